@@ -29,6 +29,17 @@ metric (BASELINE.json): "M observations/sec residual+Jacobian; wall-clock/LM-ite
           camera; no denormalised copies, no re-gathers.
   cpu_baseline: the C oracle (Ceres-semantics restatement, OpenMP) on the box's host
           cores, rank 0 at N=1 only, bounded sample.
+
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K steps and prints
+the line with the headline and the roofline of those same steps. Everything that takes runs
+of its own (lm_*, c4_*, rig_*, c2_*, cpu_baseline, c1_*) is measured only with `--full`;
+the `--no-*` options then leave single legs out.
+`--dump-outputs DIR` writes what the last timed step computed (rank 0's handle) as
+DIR/<name>.npy, float64: V [points][6] and g [points][3] (the point blocks of J^T J and
+J^T r, caller's point order), ug [free cameras][27] (U upper-packed | g_c), ux [cross][36]
+and cost [1]; an array with no entries (ux of a BAL-shaped problem) is not written. The
+problem is the seeded synthetic one, so two runs with the same arguments
+evaluate the same inputs.
 """
 import argparse
 import json
@@ -48,6 +59,10 @@ def parse():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="c3_1kcam")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the LM iterations, configs 1, 2, 4, 5 and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--lm-iters", type=int, default=5)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-lm", action="store_true")
@@ -58,7 +73,34 @@ def parse():
                     "its launches share the kernel name)")
     ap.add_argument("--rig-config", default="c5_rig_16x64")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic_latest.json"))
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:  # a plain run measures the headline only
+        args.no_cpu = args.no_lm = args.no_rig = args.no_c4 = args.no_c1 = args.no_c2 = True
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(solver, out_dir):
+    """Write the arrays of the last evaluation pass as out_dir/<name>.npy (float64). Above
+    64 MB in all, V and g keep a fixed, seeded sample of the points (point_index.npy)."""
+    import numpy as np
+    blocks = solver.bench_blocks()
+    rest = sum(blocks[k].nbytes for k in ("ug", "ux", "cost"))
+    npts = blocks["V"].shape[0]
+    keep = int((DUMP_LIMIT_BYTES - rest - 4096) // (8 * (6 + 3 + 1)))  # 4096: the .npy headers
+    if keep < npts:
+        idx = np.sort(np.random.default_rng(0).choice(npts, size=keep, replace=False))
+        blocks["V"], blocks["g"] = blocks["V"][idx], blocks["g"][idx]
+        blocks["point_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in blocks.items():
+        if a.size == 0:  # a BAL-shaped problem has no cross blocks: no empty ux.npy
+            continue
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def launch_ranks(args):
@@ -167,6 +209,8 @@ def main():
     achieved = jac_bytes / (jac_ms * 1e-3) / 1e9
     fused = solver.eval_fused()
     eval_kernel = "k_eval_bal" if fused else "k_eval_points"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(solver, args.dump_outputs)
 
     # ---- LM iterations (wall-clock per iteration, same problem) ----
     # "lm_*": exact reduced-camera solve (dense Schur + device Cholesky, the reference's

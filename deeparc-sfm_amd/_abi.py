@@ -114,6 +114,7 @@ SIGNATURES = {
     "dab_dense_spd_solve": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]),
     "dab_bench_eval_pass": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "dab_sync": (C.c_int, [C.c_void_p]),
+    "dab_bench_get_blocks": (C.c_int, [C.c_void_p, _ip, _ip, _dp, _dp, _dp, _dp, _dp]),
     "dab_bench_kernel_ms": (C.c_int, [C.c_void_p, _dp, _dp]),
     "dab_jacobian_bytes": (C.c_int, [C.c_void_p, _dp]),
     "dab_bench_pair_ms": (C.c_int, [C.c_void_p, _dp, _dp]),

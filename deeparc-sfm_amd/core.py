@@ -291,6 +291,20 @@ class Solver:
     def sync(self):
         check(self.lib.dab_sync(self.h), self.lib)
 
+    def bench_blocks(self):
+        """What the last evaluation pass computed (dab_bench_get_blocks): V [points][6],
+        g [points][3], ug [free ext][27], ux [cross][36] and the cost."""
+        nc, nx = C.c_int32(), C.c_int32()
+        check(self.lib.dab_bench_get_blocks(self.h, C.byref(nc), C.byref(nx), None, None, None, None, None),
+              self.lib)
+        npts = self.problem.points.shape[0]
+        V, g = np.zeros((npts, 6)), np.zeros((npts, 3))
+        ug, ux = np.zeros((nc.value, 27)), np.zeros((nx.value, 36))
+        cost = C.c_double()
+        check(self.lib.dab_bench_get_blocks(self.h, None, None, _ptr(V, C.c_double), _ptr(g, C.c_double),
+                                            _ptr(ug, C.c_double), _ptr(ux, C.c_double), C.byref(cost)), self.lib)
+        return {"V": V, "g": g, "ug": ug, "ux": ux, "cost": np.array([cost.value])}
+
     def bench_kernel_ms(self):
         a, b = C.c_double(), C.c_double()
         check(self.lib.dab_bench_kernel_ms(self.h, C.byref(a), C.byref(b)), self.lib)

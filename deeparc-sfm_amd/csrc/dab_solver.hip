@@ -3624,6 +3624,49 @@ extern "C" int dab_sync(dab_handle* h) {
   return 0;
 }
 
+extern "C" int dab_bench_get_blocks(dab_handle* h, int32_t* num_free_ext, int32_t* num_cross, double* V, double* g,
+                                    double* ug, double* ux, double* cost) {
+  clear_error();
+  if (!h || !h->have_problem) return set_error(DAB_E_STATE, "no problem set");
+  HIP_OK(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  if (num_free_ext) *num_free_ext = h->NC;
+  if (num_cross) *num_cross = h->ncross;
+  const size_t NP = (size_t)h->NP;
+  if (V || g) {
+    std::vector<double> hv(6 * NP), hg(3 * NP);
+    if (NP > 0) {
+      HIP_OK(hipMemcpyAsync(hv.data(), h->d_V, hv.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+      HIP_OK(hipMemcpyAsync(hg.data(), h->d_g, hg.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+      HIP_OK(hipStreamSynchronize(s));
+    }
+    const size_t npts = (size_t)h->prob.num_points;
+    if (V) std::fill(V, V + 6 * npts, 0.0);
+    if (g) std::fill(g, g + 3 * npts, 0.0);
+    for (size_t i = 0; i < NP; ++i) {
+      const size_t p = (size_t)h->pt_of[i];
+      if (V)
+        for (int k = 0; k < 6; ++k) V[6 * p + k] = hv[k * NP + i];
+      if (g)
+        for (int k = 0; k < 3; ++k) g[3 * p + k] = hg[k * NP + i];
+    }
+  }
+  if (ug && h->NC > 0)
+    HIP_OK(hipMemcpyAsync(ug, h->ug(), sizeof(double) * 27 * (size_t)h->NC, hipMemcpyDeviceToHost, s));
+  if (ux && h->NC > 0 && h->ncross > 0)
+    HIP_OK(hipMemcpyAsync(ux, h->Ux(), sizeof(double) * 36 * (size_t)h->ncross, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  if (cost) {
+    // read_scalars converts a fixed-point cost once and clears the flag: put it back, so
+    // that this read leaves the handle as it found it
+    const bool pending = h->cost_fx_pending;
+    CHECK_RC(read_scalars(h));
+    h->cost_fx_pending = pending;
+    *cost = 0.5 * h->h_scal[S_COST];
+  }
+  return 0;
+}
+
 extern "C" int dab_bench_kernel_ms(dab_handle* h, double* jac_ms, double* assembly_ms) {
   clear_error();
   if (!h) return set_error(DAB_E_INVALID, "null handle");

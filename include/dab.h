@@ -269,6 +269,15 @@ int dab_dense_spd_solve(dab_handle* h, int n, const double* A, const double* b, 
  * batch keeps the host's launch cost off the device's critical path. */
 int dab_bench_eval_pass(dab_handle* h, int with_assembly, int count);
 int dab_sync(dab_handle* h);
+/* What the last evaluation pass left on the device, copied to host arrays (the benchmark's
+ * output dump; waits for the handle's stream). V[num_points][6] (upper-packed 3 x 3 point
+ * blocks) and g[num_points][3] in the caller's point order, zero for points of no
+ * observation on this rank; ug[*num_free_ext][27] (U upper-packed (21) | g_c (6) per free
+ * extrinsic in ascending index, summed over the ranks); ux[*num_cross][36] (the arc-ring cross blocks);
+ * *cost = 0.5 * sum r^2. Every pointer may be NULL: query the two counts first, then call
+ * again with arrays of those sizes. The handle's state is unchanged. */
+int dab_bench_get_blocks(dab_handle* h, int32_t* num_free_ext, int32_t* num_cross, double* V, double* g,
+                         double* ug, double* ux, double* cost);
 /* Kernel timing: average device time (ms) of the point-side residual+Jacobian kernel and
  * of the rest of the pass, over the passes since the last call, measured with HIP events on
  * the handle's stream (every 8th pass of a dab_bench_eval_pass batch and its first one;

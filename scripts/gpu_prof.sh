@@ -14,8 +14,8 @@ timeout -k 10 600 rocprofv3 --pmc SQ_INSTS_VALU -d $OUT/valu -o run --output-for
 python3 scripts/traffic.py $OUT/fetch $OUT/write profiles/traffic_latest.json --valu-dir $OUT/valu --lib deeparc-sfm_amd/libdab.so > $OUT/traffic.txt 2>&1 || { cat $OUT/traffic.txt; exit 1; }
 cp profiles/traffic_latest.json $OUT/  # copy it back into profiles/ here (only gpurun_out/ returns)
 head -25 $OUT/traffic.txt
-timeout -k 10 600 python3 bench.py ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 600 python3 bench.py --full ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -20 $OUT/bench.err; exit 1; }
 cat $OUT/bench.json
-timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 bench.py --no-cpu --no-c2 ${PROF_ARGS} > $OUT/trace.log 2>&1 || { echo "trace pass failed"; tail -20 $OUT/trace.log; exit 1; }
+timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 bench.py --full --no-cpu --no-c2 ${PROF_ARGS} > $OUT/trace.log 2>&1 || { echo "trace pass failed"; tail -20 $OUT/trace.log; exit 1; }
 find $OUT/trace -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats.csv \;
 head -30 $OUT/kernel_stats.csv

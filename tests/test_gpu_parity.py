@@ -93,6 +93,69 @@ def test_residual_pass_vs_oracle(pkg, orc, gpu):
     assert cost == pytest.approx(co, rel=1e-12)
 
 
+@pytest.mark.parametrize("kind", ["bal", "rig"])
+def test_bench_blocks_match_jacobian_kernel(pkg, gpu, kind):
+    """dab_bench_get_blocks (the benchmark's output dump) returns what one evaluation pass
+    left on the device: the point blocks V = J_p^T J_p (upper-packed) and g = J_p^T r in the
+    caller's point order, per free extrinsic (ascending index) U = J_c^T J_c upper-packed |
+    g_c = J_c^T r, the cross blocks and the cost, against the same sums formed on the host
+    from dab_eval_jacobians' rows. Both sides are fp64 and differ in summation order and in
+    how the camera tables are built: 1e-9 relative to each array's largest entry, the bound
+    this file uses between two Jacobian evaluations."""
+    if kind == "bal":
+        prob = pkg.synth(kind=0, num_cameras=33, num_points=1500, obs_per_point=5, seed=21)
+    else:
+        prob = pkg.synth(kind=1, num_arcs=4, num_rings=7, num_points=1500, obs_per_point=6, seed=22)
+    s = pkg.Solver(0)
+    try:
+        s.set_problem(prob)
+        s.bench_eval_pass(True, 2)
+        s.sync()
+        b = s.bench_blocks()
+        b2 = s.bench_blocks()  # reading leaves the handle as it was
+        r, J = s.jacobians()
+    finally:
+        s.close()
+    for k in b:
+        np.testing.assert_array_equal(b[k], b2[k])
+    iu3, iu6 = np.triu_indices(3), np.triu_indices(6)
+    npts, next_ = prob.points.shape[0], prob.ext.shape[0]
+    Jp = J[:, :, :3]
+    V = np.zeros((npts, 3, 3))
+    g = np.zeros((npts, 3))
+    np.add.at(V, prob.obs_point, np.einsum("oki,okj->oij", Jp, Jp))
+    np.add.at(g, prob.obs_point, np.einsum("oki,ok->oi", Jp, r))
+    U = np.zeros((next_, 6, 6))
+    gc = np.zeros((next_, 6))
+    ref = np.zeros(next_, bool)
+    for ext, cols in ((prob.obs_ext0, slice(3, 9)), (prob.obs_ext1, slice(9, 15))):
+        m = ext >= 0
+        Jc = J[m][:, :, cols]
+        np.add.at(U, ext[m], np.einsum("oki,okj->oij", Jc, Jc))
+        np.add.at(gc, ext[m], np.einsum("oki,ok->oi", Jc, r[m]))
+        ref[ext[m]] = True
+    const = np.zeros(next_, bool) if prob.ext_const is None else prob.ext_const.astype(bool)
+    free = np.flatnonzero(ref & ~const)
+    both = (prob.obs_ext1 >= 0) & ~const[prob.obs_ext0] & ~const[np.maximum(prob.obs_ext1, 0)]
+    cross = np.einsum("oki,okj->", J[both][:, :, 3:9], J[both][:, :, 9:15])
+
+    def close(a, ref_):
+        scale = np.abs(ref_).max()
+        assert np.abs(a - ref_).max() <= 1e-9 * scale, (np.abs(a - ref_).max(), scale)
+
+    assert b["cost"][0] == pytest.approx(0.5 * (r * r).sum(), rel=1e-12)
+    close(b["V"], V[:, iu3[0], iu3[1]])
+    close(b["g"], g)
+    assert b["ug"].shape == (len(free), 27)
+    close(b["ug"][:, :21], U[free][:, iu6[0], iu6[1]])
+    close(b["ug"][:, 21:], gc[free])
+    if kind == "rig":
+        assert b["ux"].shape[0] > 0
+        assert abs(b["ux"].sum() - cross) <= 1e-9 * np.abs(b["ux"]).sum()
+    else:
+        assert b["ux"].shape == (0, 36)
+
+
 def run_both(pkg, orc, prob, **kw):
     ref = prob.copy()
     opts = pkg.options(num_threads=8, **kw)
