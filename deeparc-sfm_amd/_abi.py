@@ -18,6 +18,25 @@ DAB_CONVERGENCE = 0
 DAB_NO_CONVERGENCE = 1
 DAB_FAILURE = 2
 TERMINATION = {0: "CONVERGENCE", 1: "NO_CONVERGENCE", 2: "FAILURE"}
+DAB_E_INVALID = -1
+DAB_E_UNSUPPORTED = -6
+DAB_LOSS_TRIVIAL = 0
+DAB_LOSS_HUBER = 1
+DAB_LOSS_SOFT_L1 = 2
+DAB_LOSS_CAUCHY = 3
+LOSS_KINDS = {"trivial": DAB_LOSS_TRIVIAL, "huber": DAB_LOSS_HUBER, "soft_l1": DAB_LOSS_SOFT_L1,
+              "cauchy": DAB_LOSS_CAUCHY}
+
+
+def loss_kind(kind):
+    """DAB_LOSS_* of a loss given by name ("cauchy"), by number, or None (trivial)."""
+    if kind is None:
+        return DAB_LOSS_TRIVIAL
+    if isinstance(kind, str):
+        if kind.lower() not in LOSS_KINDS:
+            raise ValueError(f"unknown loss {kind!r}: one of {sorted(LOSS_KINDS)}")
+        return LOSS_KINDS[kind.lower()]
+    return int(kind)
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -107,6 +126,8 @@ SIGNATURES = {
     "dab_set_problem": (C.c_int, [C.c_void_p, C.POINTER(DabProblem)]),
     "dab_update_parameters": (C.c_int, [C.c_void_p, _dp, _dp]),
     "dab_solve": (C.c_int, [C.c_void_p, C.POINTER(DabOptions), C.POINTER(DabSummary)]),
+    "dab_set_loss": (C.c_int, [C.c_void_p, C.c_int32, C.c_double]),
+    "dab_get_loss": (C.c_int, [C.c_void_p, _ip, _dp]),
     "dab_get_parameters": (C.c_int, [C.c_void_p, _dp, _dp]),
     "dab_eval_residuals": (C.c_int, [C.c_void_p, _dp, _dp]),
     "dab_eval_jacobians": (C.c_int, [C.c_void_p, _dp, _dp]),

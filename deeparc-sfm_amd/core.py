@@ -234,6 +234,19 @@ class Solver:
             self.h, _ptr(np.ascontiguousarray(points, np.float64), C.c_double) if points is not None else None,
             _ptr(np.ascontiguousarray(ext, np.float64), C.c_double) if ext is not None else None), self.lib)
 
+    def set_loss(self, kind, scale=1.0):
+        """Robust loss of every observation (dab_set_loss): kind "trivial" | "huber" | "soft_l1" |
+        "cauchy" (or a DAB_LOSS_* number, or None = trivial), scale = Ceres' `a`. State of the
+        handle: it survives set_problem and holds for every later solve until set again."""
+        check(self.lib.dab_set_loss(self.h, _abi.loss_kind(kind), float(scale)), self.lib)
+
+    def get_loss(self):
+        """(kind name, scale) of the handle's loss; ("trivial", 0.0) when none is set."""
+        k, a = C.c_int32(), C.c_double()
+        check(self.lib.dab_get_loss(self.h, C.byref(k), C.byref(a)), self.lib)
+        names = {v: n for n, v in _abi.LOSS_KINDS.items()}
+        return names[k.value], a.value
+
     def solve(self, opts=None, max_records=1024):
         o = opts if opts is not None else options()
         its = (DabIteration * max_records)()
@@ -341,14 +354,18 @@ class Solver:
 
 
 def solve(problem, max_iteration=1000, max_second=3600, freeze_camera=False, device=0,
-          verbose=False, **opt_kw):
+          verbose=False, loss=None, **opt_kw):
     """Drop-in for the reference's solve() (src/sfm.cc:31): DENSE_SCHUR-equivalent LM,
-    max_num_iterations / max_solver_time_in_seconds as given, parameters updated in place."""
+    max_num_iterations / max_solver_time_in_seconds as given, parameters updated in place.
+    loss: None (the reference's NULL loss, sfm.cc:48) or a (kind, scale) pair such as
+    ("cauchy", 0.5), the `new ceres::CauchyLoss(0.5)` the reference keeps commented out."""
     problem.freeze_camera = bool(freeze_camera)
     o = options(max_num_iterations=max_iteration, max_solver_time_in_seconds=float(max_second),
                 minimizer_progress_to_stdout=int(verbose), **opt_kw)
     s = Solver(device)
     try:
+        if loss is not None:
+            s.set_loss(*loss)
         s.set_problem(problem)
         return s.solve(o)
     finally:

@@ -5,7 +5,19 @@
 
 #include <cstdint>
 
+#include "../../include/dab.h"
+
 namespace dab {
+
+// Host dispatch of a kernel's loss instantiation: runs `...` with LOSS a constant expression
+// equal to loss_ (a DAB_LOSS_*; dab_set_loss admits no other value).
+#define DAB_LOSS_SWITCH(loss_, ...)                                                          \
+  switch (loss_) {                                                                           \
+    case DAB_LOSS_HUBER: { constexpr int LOSS = DAB_LOSS_HUBER; __VA_ARGS__; } break;         \
+    case DAB_LOSS_SOFT_L1: { constexpr int LOSS = DAB_LOSS_SOFT_L1; __VA_ARGS__; } break;     \
+    case DAB_LOSS_CAUCHY: { constexpr int LOSS = DAB_LOSS_CAUCHY; __VA_ARGS__; } break;       \
+    default: { constexpr int LOSS = DAB_LOSS_TRIVIAL; __VA_ARGS__; } break;                   \
+  }
 
 constexpr int kCamTab = 32;   // doubles per extrinsic table: R(9) t(3) Rd(9) Jd(9) pad(2)
 constexpr int kIntr = 8;      // doubles per intrinsic: cx cy fx fy k0 k1 0 0
@@ -86,6 +98,11 @@ struct DevView {
   const int2* chunk_uni;    // [nchunk] (ext, intr) shared by every entry of the chunk, or (-1, -1)
   const int* obs_e;         // [N] (streamed fused pass; null otherwise) ext0 | intr << 16 of a
                             // single-extrinsic slot, -1 for padding
+  // robust loss of the handle (dab_set_loss), written into the view by the calls it takes
+  // effect at: DAB_LOSS_* and a = scale, b = a^2, c = 1 / b. The launchers pick each kernel's
+  // instantiation from loss; the kernels read a, b, c (wave-uniform) only when it is not TRIVIAL.
+  int loss;
+  double loss_a, loss_b, loss_c;
 };
 
 // camera-side chunks split by whether one camera/intrinsic serves the whole chunk

@@ -359,10 +359,43 @@ void launch_cam_tables(hipStream_t s, int E, const double* ext, double* camtab) 
 struct Proj {
   double ru, rv;
   double A0[3], A1[3];  // d(ru,rv)/dP
+  double rho;           // rho(ru^2 + rv^2) of the raw residual; set under a non-trivial loss only
 };
 
+// Robust loss (dab_set_loss), Ceres' definitions over s = ru^2 + rv^2 with a = scale, b = a^2,
+// c = 1 / b: rho(s) and rho'(s). Every one has rho'' <= 0, so Ceres' Corrector takes its
+// first branch (alpha = 0): the minimiser sees sqrt(rho') r and sqrt(rho') J, and the cost is
+// 0.5 sum rho. LOSS is a compile-time parameter of every kernel that evaluates rows: the
+// TRIVIAL instantiations contain none of this.
+struct LossK {
+  double a, b, c;
+};
+__device__ __forceinline__ LossK loss_of(const DevView& v) { return LossK{v.loss_a, v.loss_b, v.loss_c}; }
+template <int LOSS>
+__device__ __forceinline__ void loss_eval(const LossK& lk, double s, double& rho, double& rho1) {
+  static_assert(LOSS == DAB_LOSS_HUBER || LOSS == DAB_LOSS_SOFT_L1 || LOSS == DAB_LOSS_CAUCHY, "loss");
+  if constexpr (LOSS == DAB_LOSS_HUBER) {
+    // both branches by select: s = 0 (a / 0) never reaches a sum
+    const double r = sqrt(s);
+    const bool in = s <= lk.b;
+    rho = in ? s : 2.0 * lk.a * r - lk.b;
+    rho1 = in ? 1.0 : fmax(DBL_MIN, lk.a / r);
+  } else if constexpr (LOSS == DAB_LOSS_SOFT_L1) {
+    const double t = sqrt(1.0 + s * lk.c);
+    rho = 2.0 * lk.b * (t - 1.0);
+    rho1 = fmax(DBL_MIN, 1.0 / t);
+  } else {
+    const double u = 1.0 + s * lk.c;
+    rho = lk.b * log(u);
+    rho1 = fmax(DBL_MIN, 1.0 / u);
+  }
+}
+
+// LOSS != TRIVIAL: o.rho = rho(s) of the raw residual; with want_jac the residual and the rows
+// leave scaled by sqrt(rho'(s)) (without it, the candidate's residual stays raw: only rho is used)
+template <int LOSS = DAB_LOSS_TRIVIAL>
 __device__ __forceinline__ void project(const double P[3], const double* __restrict__ K, double ox,
-                                        double oy, Proj& o, bool want_jac) {
+                                        double oy, Proj& o, bool want_jac, const LossK& lk = LossK{}) {
   const double cx = K[0], cy = K[1], fx = K[2], fy = K[3], k0 = K[4], k1 = K[5];
   // one reciprocal for the perspective divide and its derivative: v_rcp_f64 refined by
   // two Newton steps (within 1 ulp of the two divisions of the functor; 5 instructions
@@ -377,6 +410,8 @@ __device__ __forceinline__ void project(const double P[3], const double* __restr
   const double d = 1.0 + r2 * (k0 + k1 * r2);
   o.ru = fx * d * xp + cx - ox;
   o.rv = fy * d * yp + cy - oy;
+  double rho1 = 1.0;
+  if constexpr (LOSS != DAB_LOSS_TRIVIAL) loss_eval<LOSS>(lk, o.ru * o.ru + o.rv * o.rv, o.rho, rho1);
   if (!want_jac) return;
   const double dd = k0 + 2.0 * k1 * r2;
   const double du_dx = fx * (d + 2.0 * xp * xp * dd), du_dy = fx * (2.0 * xp * yp * dd);
@@ -387,6 +422,16 @@ __device__ __forceinline__ void project(const double P[3], const double* __restr
   o.A1[0] = dv_dx * iz;
   o.A1[1] = dv_dy * iz;
   o.A1[2] = -(dv_dx * xp + dv_dy * yp) * iz;
+  if constexpr (LOSS != DAB_LOSS_TRIVIAL) {
+    const double w = sqrt(rho1);
+    o.ru *= w;
+    o.rv *= w;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      o.A0[i] *= w;
+      o.A1[i] *= w;
+    }
+  }
 }
 
 __device__ __forceinline__ void rowmat(const double a[3], const double* __restrict__ M, double o[3]) {
@@ -586,10 +631,13 @@ struct LdsTabs {
 // X (single) or P2 = R1 X + t1 (arc∘ring).
 // MAYCOMP = false: the caller knows no observation is arc∘ring (ext1 < 0 everywhere), so
 // the second table is never read and its registers are never allocated.
-template <bool JP, int SLOT, class Tabs, bool MAYCOMP = true>
-__device__ __forceinline__ void obs_rows(const int4 id, const double2 xy, const double X[3], const Tabs& tb,
-                                         double& ru, double& rv, double jx0[3], double jx1[3], double jc0[6],
-                                         double jc1[6], double jd0[6] = nullptr, double jd1[6] = nullptr) {
+// obs_rows_l: the same under loss LOSS — residual and rows scaled by sqrt(rho') (project), rho
+// = rho(s) of the raw residual (untouched for TRIVIAL, where obs_rows_l IS obs_rows).
+template <int LOSS, bool JP, int SLOT, bool MAYCOMP = true, class Tabs>
+__device__ __forceinline__ void obs_rows_l(const LossK& lk, double& rho, const int4 id, const double2 xy,
+                                           const double X[3], const Tabs& tb, double& ru, double& rv,
+                                           double jx0[3], double jx1[3], double jc0[6], double jc1[6],
+                                           double jd0[6] = nullptr, double jd1[6] = nullptr) {
   const bool comp = MAYCOMP && id.z >= 0;
   double A[12];  // R0 | t0
   tb.rt(id.y, A);
@@ -607,9 +655,10 @@ __device__ __forceinline__ void obs_rows(const int4 id, const double2 xy, const 
   double P[3];
   matvec_add(A, Q, A + 9, P);
   Proj pr;
-  project(P, Kr, xy.x, xy.y, pr, true);
+  project<LOSS>(P, Kr, xy.x, xy.y, pr, true, lk);
   ru = pr.ru;
   rv = pr.rv;
+  if constexpr (LOSS != DAB_LOSS_TRIVIAL) rho = pr.rho;
   if constexpr (SLOT == 0 || SLOT == 2) {
     double D[18];  // Rd0 | Jd0
     tb.dj(id.y, D);
@@ -667,12 +716,20 @@ __device__ __forceinline__ void obs_rows(const int4 id, const double2 xy, const 
   }
 }
 
+template <bool JP, int SLOT, class Tabs, bool MAYCOMP = true>
+__device__ __forceinline__ void obs_rows(const int4 id, const double2 xy, const double X[3], const Tabs& tb,
+                                         double& ru, double& rv, double jx0[3], double jx1[3], double jc0[6],
+                                         double jc1[6], double jd0[6] = nullptr, double jd1[6] = nullptr) {
+  double rho;
+  obs_rows_l<DAB_LOSS_TRIVIAL, JP, SLOT, MAYCOMP>(LossK{}, rho, id, xy, X, tb, ru, rv, jx0, jx1, jc0, jc1, jd0, jd1);
+}
+
 // Every row of one observation (parity API, cross blocks, candidate pass).
-template <class Tabs>
+template <int LOSS = DAB_LOSS_TRIVIAL, class Tabs>
 __device__ __forceinline__ void obs_jacobian_t(const int4 id, const double2 xy, const double X[3], const Tabs& tb,
-                                               ObsJac& o) {
+                                               ObsJac& o, const LossK& lk = LossK{}) {
   double c0[6], c1[6], d0[6], d1[6];
-  obs_rows<true, 2>(id, xy, X, tb, o.pr.ru, o.pr.rv, o.jx0, o.jx1, c0, c1, d0, d1);
+  obs_rows_l<LOSS, true, 2>(lk, o.pr.rho, id, xy, X, tb, o.pr.ru, o.pr.rv, o.jx0, o.jx1, c0, c1, d0, d1);
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
     o.jw0a[i] = c0[i];
@@ -700,7 +757,7 @@ __device__ __forceinline__ void obs_jacobian(const int4 id, const double2 xy, co
 // and the per-wave sums are combined in LDS (sh[WPS-1][9][64]) in a fixed order: no
 // cross-lane scan. Every wave of the work-group calls this the same number of times
 // (sl >= nslice: no work, barriers only).
-template <int WPS, int VAR, class Tabs>
+template <int WPS, int VAR, int LOSS = DAB_LOSS_TRIVIAL, class Tabs>
 __device__ __forceinline__ void eval_slice(const DevView& v, const double* __restrict__ points, const Tabs& tabs,
                                            double* __restrict__ V, double* __restrict__ g, int sl, int w,
                                            double (*sh)[9][64], double (&acc)[2]) {
@@ -708,6 +765,7 @@ __device__ __forceinline__ void eval_slice(const DevView& v, const double* __res
   const size_t NPs = (size_t)v.NP;
   const bool live = sl < v.nslice;
   const int p = 64 * sl + lane;
+  const LossK lk = loss_of(v);
   double c[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) c[k] = 0.0;
@@ -735,7 +793,7 @@ __device__ __forceinline__ void eval_slice(const DevView& v, const double* __res
         xy_n = v.obs_xy[off + 64 * (k + WPS) + lane];
       }
       if (id.x < 0) continue;  // padding slot
-      double ru, rv, jx0[3], jx1[3];
+      double ru, rv, jx0[3], jx1[3], rho = 0.0;
       if constexpr (VAR == 1) {  // ablation: loads only
         ru = xy.x + id.y;
         rv = xy.y + id.w;
@@ -743,7 +801,7 @@ __device__ __forceinline__ void eval_slice(const DevView& v, const double* __res
         for (int q = 0; q < 3; ++q) jx0[q] = jx1[q] = X[q];
       } else {
         if constexpr (VAR == 2) id.y = id.w = 0;  // ablation: one camera (uniform table loads)
-        obs_rows<true, -1>(id, xy, X, tabs, ru, rv, jx0, jx1, nullptr, nullptr);
+        obs_rows_l<LOSS, true, -1>(lk, rho, id, xy, X, tabs, ru, rv, jx0, jx1, nullptr, nullptr);
       }
       // accumulate as two fused multiply-adds per entry (row 0, then row 1)
       c[0] = fma(jx1[0], jx1[0], fma(jx0[0], jx0[0], c[0]));
@@ -755,7 +813,8 @@ __device__ __forceinline__ void eval_slice(const DevView& v, const double* __res
       c[6] = fma(jx1[0], rv, fma(jx0[0], ru, c[6]));
       c[7] = fma(jx1[1], rv, fma(jx0[1], ru, c[7]));
       c[8] = fma(jx1[2], rv, fma(jx0[2], ru, c[8]));
-      acc[0] = fma(rv, rv, fma(ru, ru, acc[0]));
+      if constexpr (LOSS == DAB_LOSS_TRIVIAL) acc[0] = fma(rv, rv, fma(ru, ru, acc[0]));
+      else acc[0] += rho;  // the cost is 0.5 sum rho(s), not 0.5 |scaled r|^2
       acc[1] += (isfinite(ru) && isfinite(rv)) ? 0.0 : 1.0;
     }
   }
@@ -855,7 +914,7 @@ __device__ __forceinline__ void store_cost_partial_last(double (&acc)[2], double
 }
 
 // tables from global memory: one block per slice, grid-strided
-template <int WPS, int VAR = 0>
+template <int WPS, int VAR = 0, int LOSS = DAB_LOSS_TRIVIAL>
 __global__ __launch_bounds__(64 * WPS) void k_eval_points(DevView v, const double* __restrict__ points,
                                                           const double* __restrict__ camtab,
                                                           double* __restrict__ V, double* __restrict__ g,
@@ -865,7 +924,7 @@ __global__ __launch_bounds__(64 * WPS) void k_eval_points(DevView v, const doubl
   double acc[2] = {0.0, 0.0};
   const int rounds = (v.nslice + gridDim.x - 1) / gridDim.x;
   for (int r = 0; r < rounds; ++r)
-    eval_slice<WPS, VAR>(v, points, tabs, V, g, r * gridDim.x + blockIdx.x, threadIdx.x >> 6, sh, acc);
+    eval_slice<WPS, VAR, LOSS>(v, points, tabs, V, g, r * gridDim.x + blockIdx.x, threadIdx.x >> 6, sh, acc);
   store_cost_partial<WPS>(acc, partial);
 }
 
@@ -875,7 +934,7 @@ __global__ __launch_bounds__(64 * WPS) void k_eval_points(DevView v, const doubl
 // ds_read_b128 instead of 64-line L2 gathers. Persistent: one 1024-thread work-group per
 // CU, 16 / WPS slices in flight (WPS waves each, rows split, LDS-combined).
 constexpr int kLdsCams = 1024;
-template <int KI, int WPS, bool KMASK = false>  // KMASK: ablation (wrong K, all from LDS)
+template <int KI, int WPS, bool KMASK = false, int LOSS = DAB_LOSS_TRIVIAL>  // KMASK: ablation (wrong K, all from LDS)
 __global__ __launch_bounds__(1024) void k_eval_points_lds(DevView v, const double* __restrict__ points,
                                                           const double* __restrict__ ext,
                                                           const double* __restrict__ camtab,
@@ -910,7 +969,7 @@ __global__ __launch_bounds__(1024) void k_eval_points_lds(DevView v, const doubl
   const int per_wg = (v.nslice + gridDim.x - 1) / gridDim.x;
   const int rounds = (per_wg + G - 1) / G;
   for (int r = 0; r < rounds; ++r)
-    eval_slice<WPS, 0>(v, points, tabs, V, g, (r * G + grp) * gridDim.x + blockIdx.x, w, sh[grp], acc);
+    eval_slice<WPS, 0, LOSS>(v, points, tabs, V, g, (r * G + grp) * gridDim.x + blockIdx.x, w, sh[grp], acc);
   store_cost_partial_last<16>(acc, partial, arrivals, cost);
 }
 
@@ -1003,7 +1062,7 @@ __device__ __forceinline__ void rowq_fill(const DevView& v, int off, int len, in
 // bit 1 loads only (no row math), bit 2 no table staging at all, bit 3 plain partials (no
 // cost total), bit 4 no V/g stores, bit 5 no cross-wave combine, bit 6 last-arriver cost
 // sum into cost[] instead of the fixed-point atomics (correct results)
-template <bool KL, int WPS, int D, int VAR = 0, bool COMP = true>
+template <bool KL, int WPS, int D, int VAR = 0, bool COMP = true, int LOSS = DAB_LOSS_TRIVIAL>
 __global__ __launch_bounds__(1024) void k_eval_points_pf(DevView v, const double* __restrict__ points,
                                                          const double* __restrict__ ext,
                                                          double* __restrict__ V, double* __restrict__ g,
@@ -1081,6 +1140,7 @@ __global__ __launch_bounds__(1024) void k_eval_points_pf(DevView v, const double
   }
   __syncthreads();
   const LdsTabs<KL> tabs{rt_s, k_s, nullptr, v.intr};
+  const LossK lk = loss_of(v);
   double acc[2] = {0.0, 0.0};
   for (int r = 0; r < rounds; ++r) {
     if (r > 0) {
@@ -1121,16 +1181,17 @@ __global__ __launch_bounds__(1024) void k_eval_points_pf(DevView v, const double
         // branch-free: padding slots (point -1; ext0 = intr = 0, ext1 = -1) are evaluated
         // and dropped by selects, so the row has no exec-mask branch around it
         const bool live = id.x >= 0;
-        double ru, rv, jx0[3], jx1[3];
+        double ru, rv, jx0[3], jx1[3], rho = 0.0;
         if constexpr (VAR & 2) {
           ru = xy.x + id.y;
           rv = xy.y + id.w;
 #pragma unroll
           for (int q = 0; q < 3; ++q) jx0[q] = jx1[q] = X[q];
         } else {
-          obs_rows<true, -1, LdsTabs<KL>, COMP>(id, xy, X, tabs, ru, rv, jx0, jx1, nullptr, nullptr);
+          obs_rows_l<LOSS, true, -1, COMP>(lk, rho, id, xy, X, tabs, ru, rv, jx0, jx1, nullptr, nullptr);
         }
         if (!live) ru = rv = jx0[0] = jx0[1] = jx0[2] = jx1[0] = jx1[1] = jx1[2] = 0.0;
+        if constexpr (LOSS != DAB_LOSS_TRIVIAL) rho = live ? rho : 0.0;
         c[0] = fma(jx1[0], jx1[0], fma(jx0[0], jx0[0], c[0]));
         c[1] = fma(jx1[0], jx1[1], fma(jx0[0], jx0[1], c[1]));
         c[2] = fma(jx1[0], jx1[2], fma(jx0[0], jx0[2], c[2]));
@@ -1140,7 +1201,8 @@ __global__ __launch_bounds__(1024) void k_eval_points_pf(DevView v, const double
         c[6] = fma(jx1[0], rv, fma(jx0[0], ru, c[6]));
         c[7] = fma(jx1[1], rv, fma(jx0[1], ru, c[7]));
         c[8] = fma(jx1[2], rv, fma(jx0[2], ru, c[8]));
-        acc[0] = fma(rv, rv, fma(ru, ru, acc[0]));
+        if constexpr (LOSS == DAB_LOSS_TRIVIAL) acc[0] = fma(rv, rv, fma(ru, ru, acc[0]));
+        else acc[0] += rho;
         acc[1] += (isfinite(ru) && isfinite(rv)) ? 0.0 : 1.0;
       }
     }
@@ -1178,49 +1240,50 @@ __global__ __launch_bounds__(1024) void k_eval_points_pf(DevView v, const double
   else cost_fx_add<16>(acc, costfx);
 }
 
-template <int WPS, int D, int VAR = 0>
+template <int WPS, int D, int VAR = 0, int LOSS = DAB_LOSS_TRIVIAL>
 static void launch_pf(hipStream_t s, const DevView& v, const double* points, const double* ext, double* V, double* g,
                       double* partial, unsigned* arrivals, double* cost, unsigned long long* costfx,
                       unsigned long long* fx_next, int grid) {
   // single-extrinsic problems: no second table, so the row queue can be 2 deeper
   if (!v.any_comp && v.NI <= kLdsCams)
-    k_eval_points_pf<true, WPS, D + 2, VAR, false>
+    k_eval_points_pf<true, WPS, D + 2, VAR, false, LOSS>
         <<<grid, 1024, 0, s>>>(v, points, ext, V, g, partial, arrivals, cost, costfx, fx_next);
   else if (v.NI <= kLdsCams)
-    k_eval_points_pf<true, WPS, D, VAR><<<grid, 1024, 0, s>>>(v, points, ext, V, g, partial, arrivals, cost, costfx, fx_next);
+    k_eval_points_pf<true, WPS, D, VAR, true, LOSS><<<grid, 1024, 0, s>>>(v, points, ext, V, g, partial, arrivals, cost, costfx, fx_next);
   else
-    k_eval_points_pf<false, WPS, D, VAR><<<grid, 1024, 0, s>>>(v, points, ext, V, g, partial, arrivals, cost, costfx, fx_next);
+    k_eval_points_pf<false, WPS, D, VAR, true, LOSS><<<grid, 1024, 0, s>>>(v, points, ext, V, g, partial, arrivals, cost, costfx, fx_next);
 }
 
 // LDS variants (all <= 160 KiB): wps 0 = 4 waves/slice, K staged when NI <= 128;
 // wps -1 = 1 wave/slice with every intrinsic staged (NI <= 1024); wps -2 = 2 waves/slice
-void launch_eval_points(hipStream_t s, const DevView& v, const double* points, const double* ext,
+template <int LOSS>
+static void launch_eval_points_t(hipStream_t s, const DevView& v, const double* points, const double* ext,
                         const double* camtab, double* V, double* g, double* partial, unsigned* arrivals,
                         double* cost, unsigned long long* costfx, unsigned long long* fx_next, int grid,
                         int wps) {
   if (wps == 0 || wps == -2) {  // LDS tables built in-kernel; grid = persistent work-groups
     if (wps == 0) {
-      if (v.NI <= 128) k_eval_points_lds<128, 4><<<grid, 1024, 0, s>>>(v, points, ext, camtab, V, g, partial, arrivals, cost);
-      else k_eval_points_lds<0, 4><<<grid, 1024, 0, s>>>(v, points, ext, camtab, V, g, partial, arrivals, cost);
+      if (v.NI <= 128) k_eval_points_lds<128, 4, false, LOSS><<<grid, 1024, 0, s>>>(v, points, ext, camtab, V, g, partial, arrivals, cost);
+      else k_eval_points_lds<0, 4, false, LOSS><<<grid, 1024, 0, s>>>(v, points, ext, camtab, V, g, partial, arrivals, cost);
     } else {
-      if (v.NI <= 128) k_eval_points_lds<128, 2><<<grid, 1024, 0, s>>>(v, points, ext, camtab, V, g, partial, arrivals, cost);
-      else k_eval_points_lds<0, 2><<<grid, 1024, 0, s>>>(v, points, ext, camtab, V, g, partial, arrivals, cost);
+      if (v.NI <= 128) k_eval_points_lds<128, 2, false, LOSS><<<grid, 1024, 0, s>>>(v, points, ext, camtab, V, g, partial, arrivals, cost);
+      else k_eval_points_lds<0, 2, false, LOSS><<<grid, 1024, 0, s>>>(v, points, ext, camtab, V, g, partial, arrivals, cost);
     }
     return;
   }
   if (wps <= -100) {  // deep-prefetch variants: -(100 + 10 WPS + D + 1000 VAR)
     switch (-wps - 100) {
-      case 12: launch_pf<1, 2>(s, v, points, ext, V, g, partial, arrivals, cost, costfx, fx_next, grid); break;
-      case 13: launch_pf<1, 3>(s, v, points, ext, V, g, partial, arrivals, cost, costfx, fx_next, grid); break;
-      case 23: launch_pf<2, 3>(s, v, points, ext, V, g, partial, arrivals, cost, costfx, fx_next, grid); break;
-      case 64012: launch_pf<1, 2, 64>(s, v, points, ext, V, g, partial, arrivals, cost, costfx, fx_next, grid); break;
-      case 64022: launch_pf<2, 2, 64>(s, v, points, ext, V, g, partial, arrivals, cost, costfx, fx_next, grid); break;
+      case 12: launch_pf<1, 2, 0, LOSS>(s, v, points, ext, V, g, partial, arrivals, cost, costfx, fx_next, grid); break;
+      case 13: launch_pf<1, 3, 0, LOSS>(s, v, points, ext, V, g, partial, arrivals, cost, costfx, fx_next, grid); break;
+      case 23: launch_pf<2, 3, 0, LOSS>(s, v, points, ext, V, g, partial, arrivals, cost, costfx, fx_next, grid); break;
+      case 64012: launch_pf<1, 2, 64, LOSS>(s, v, points, ext, V, g, partial, arrivals, cost, costfx, fx_next, grid); break;
+      case 64022: launch_pf<2, 2, 64, LOSS>(s, v, points, ext, V, g, partial, arrivals, cost, costfx, fx_next, grid); break;
 #ifdef DAB_ABLATIONS  // timing ablations (wrong results)
       case 2012: launch_pf<1, 2, 2>(s, v, points, ext, V, g, partial, arrivals, cost, costfx, fx_next, grid); break;
       case 4012: launch_pf<1, 2, 4>(s, v, points, ext, V, g, partial, arrivals, cost, costfx, fx_next, grid); break;
       case 1012: launch_pf<1, 2, 1>(s, v, points, ext, V, g, partial, arrivals, cost, costfx, fx_next, grid); break;
 #endif
-      default: launch_pf<2, 2>(s, v, points, ext, V, g, partial, arrivals, cost, costfx, fx_next, grid); break;
+      default: launch_pf<2, 2, 0, LOSS>(s, v, points, ext, V, g, partial, arrivals, cost, costfx, fx_next, grid); break;
     }
     return;
   }
@@ -1237,13 +1300,20 @@ void launch_eval_points(hipStream_t s, const DevView& v, const double* points, c
   }
 #endif
   if (wps == 16) {
-    k_eval_points<16><<<grid, 1024, 0, s>>>(v, points, camtab, V, g, partial);
+    k_eval_points<16, 0, LOSS><<<grid, 1024, 0, s>>>(v, points, camtab, V, g, partial);
   } else if (wps == 8) {
-    k_eval_points<8><<<grid, 512, 0, s>>>(v, points, camtab, V, g, partial);
+    k_eval_points<8, 0, LOSS><<<grid, 512, 0, s>>>(v, points, camtab, V, g, partial);
   } else {
-    k_eval_points<4><<<grid, 256, 0, s>>>(v, points, camtab, V, g, partial);
+    k_eval_points<4, 0, LOSS><<<grid, 256, 0, s>>>(v, points, camtab, V, g, partial);
   }
   launch_final_sum(s, grid, 2, partial, cost);
+}
+void launch_eval_points(hipStream_t s, const DevView& v, const double* points, const double* ext,
+                        const double* camtab, double* V, double* g, double* partial, unsigned* arrivals,
+                        double* cost, unsigned long long* costfx, unsigned long long* fx_next, int grid,
+                        int wps) {
+  DAB_LOSS_SWITCH(v.loss, launch_eval_points_t<LOSS>(s, v, points, ext, camtab, V, g, partial, arrivals, cost, costfx,
+                                                     fx_next, grid, wps));
 }
 bool eval_points_needs_camtab(int wps) { return wps > 0; }
 
@@ -1386,7 +1456,7 @@ void launch_filter(hipStream_t s, const DevView& v, const double* points, const 
 // blockDim.x; one wave of the fused pass: i0 = b + lane, stride = 64)
 // MakeTabs: a callable returning the table view, called after the first entry's loads
 // are issued (the fused pass builds the camera table in SGPRs while they are in flight).
-template <class MakeTabs>
+template <int LOSS = DAB_LOSS_TRIVIAL, class MakeTabs>
 __device__ __forceinline__ void eval_cams_chunk_lazy(const DevView& v, int i0, int e, int stride,
                                                      const double* __restrict__ points, MakeTabs make_tabs,
                                                      double (&acc)[27]) {
@@ -1403,6 +1473,7 @@ __device__ __forceinline__ void eval_cams_chunk_lazy(const DevView& v, int i0, i
     X_n[2] = points[3 * (size_t)id_n.x + 2];
   }
   const auto tabs = make_tabs();
+  const LossK lk = loss_of(v);
   for (; i < e; i += stride) {
     int4 id = id_n;
     const double2 xy = xy_n;
@@ -1417,9 +1488,9 @@ __device__ __forceinline__ void eval_cams_chunk_lazy(const DevView& v, int i0, i
     }
     const bool slot1 = (id.w & kSlotBit) != 0;
     id.w &= ~kSlotBit;
-    double ru, rv, ja[6], jb[6];
-    if (slot1) obs_rows<false, 1>(id, xy, X, tabs, ru, rv, nullptr, nullptr, ja, jb);
-    else obs_rows<false, 0>(id, xy, X, tabs, ru, rv, nullptr, nullptr, ja, jb);
+    double ru, rv, ja[6], jb[6], rho;
+    if (slot1) obs_rows_l<LOSS, false, 1>(lk, rho, id, xy, X, tabs, ru, rv, nullptr, nullptr, ja, jb);
+    else obs_rows_l<LOSS, false, 0>(lk, rho, id, xy, X, tabs, ru, rv, nullptr, nullptr, ja, jb);
     int k = 0;
 #pragma unroll
     for (int a = 0; a < 6; ++a)
@@ -1433,11 +1504,11 @@ __device__ __forceinline__ void eval_cams_chunk_lazy(const DevView& v, int i0, i
   }
 }
 
-template <class Tabs>
+template <int LOSS = DAB_LOSS_TRIVIAL, class Tabs>
 __device__ __forceinline__ void eval_cams_chunk(const DevView& v, int i0, int e, int stride,
                                                 const double* __restrict__ points, const Tabs& tabs,
                                                 double (&acc)[27]) {
-  eval_cams_chunk_lazy(v, i0, e, stride, points, [&]() -> const Tabs& { return tabs; }, acc);
+  eval_cams_chunk_lazy<LOSS>(v, i0, e, stride, points, [&]() -> const Tabs& { return tabs; }, acc);
 }
 
 // Uniform chunk, single-extrinsic observations (the fused pass's camera waves): entries
@@ -1447,7 +1518,7 @@ __device__ __forceinline__ void eval_cams_chunk(const DevView& v, int i0, int e,
 // pipeline waits for the next index right before every gather, i.e. one HBM latency per
 // entry; here a wait only ever covers loads issued a full step earlier. Only the point
 // index is read (cm_pt, 4 B, not the 16-B cm_idx record): the table is the chunk's.
-template <int NS = 3, class MakeTabs>
+template <int NS = 3, int LOSS = DAB_LOSS_TRIVIAL, class MakeTabs>
 __device__ __forceinline__ void eval_cams_uni_pipe(const DevView& v, int i0, int e, int stride,
                                                    const double* __restrict__ points, MakeTabs make_tabs,
                                                    double (&acc)[27]) {
@@ -1477,6 +1548,7 @@ __device__ __forceinline__ void eval_cams_uni_pipe(const DevView& v, int i0, int
       for (int q = 0; q < 3; ++q) X[s][q] = points[3 * (size_t)pt[s] + q];
     }
   const auto tabs = make_tabs();
+  const LossK lk = loss_of(v);
   DAB_STAMP_ANY(1);
   for (int i = i0; i < e; i += NS * stride) {
 #pragma unroll
@@ -1492,9 +1564,9 @@ __device__ __forceinline__ void eval_cams_uni_pipe(const DevView& v, int i0, int
         pt[sl] = cm_pt[ii + (NS - 1) * stride];
         xy[sl] = v.cm_xy[ii + (NS - 1) * stride];
       }
-      double ru, rv, ja[6], jb[6];
-      obs_rows<false, 0, UniTabs, false>(make_int4(pt[u], 0, -1, 0), xy[u], X[u], tabs, ru, rv, nullptr, nullptr,
-                                          ja, jb);
+      double ru, rv, ja[6], jb[6], rho;
+      obs_rows_l<LOSS, false, 0, false>(lk, rho, make_int4(pt[u], 0, -1, 0), xy[u], X[u], tabs, ru, rv, nullptr,
+                                        nullptr, ja, jb);
       int k = 0;
 #pragma unroll
       for (int a = 0; a < 6; ++a)
@@ -1535,8 +1607,9 @@ struct UniFrame {
   }
 };
 
+template <int LOSS = DAB_LOSS_TRIVIAL>
 __device__ __forceinline__ void frame_rows_acc(const double2 xy, const double (&X)[3], const UniFrame& f,
-                                               double (&acc)[27]) {
+                                               double (&acc)[27], const LossK& lk = LossK{}) {
   const double* R = f.T;
   double Y[3], P[3];
 #pragma unroll
@@ -1549,7 +1622,7 @@ __device__ __forceinline__ void frame_rows_acc(const double2 xy, const double (&
 #pragma unroll
   for (int r = 0; r < 3; ++r) Z[r] = f.small ? X[r] : Y[r];
   Proj pr;
-  project(P, f.K, xy.x, xy.y, pr, true);
+  project<LOSS>(P, f.K, xy.x, xy.y, pr, true, lk);  // rows linear in A, r: scaled here, J_l after the sums
   // one row at a time (the row's 6 values are all that is live beside the sums); the
   // per-element order is the two-row fma(b, b, fma(a, a, acc)) of obs_rows' callers
 #pragma unroll
@@ -1584,10 +1657,11 @@ __device__ __forceinline__ void frame_rows_acc(const double2 xy, const double (&
 // compute of step st only for its point. The camera's frame comes from the caller
 // (get_frame(), called once the first indices and gathers are in flight: k_eval_bal's frames
 // shared in LDS).
-template <class GetFrame>
+template <int LOSS = DAB_LOSS_TRIVIAL, class GetFrame>
 __device__ __forceinline__ void eval_cams_gather_f(const int* __restrict__ cm_pt, const double2* __restrict__ cmxy,
                                                    const double* __restrict__ points, int i0, int e,
-                                                   double (&acc)[27], GetFrame get_frame) {
+                                                   double (&acc)[27], GetFrame get_frame,
+                                                   const LossK& lk = LossK{}) {
   constexpr int DG = 2, DI = 4, R = 3;
   const int lo = i0 - (int)(threadIdx.x & 63);
   const int n = (e - lo + 63) >> 6;  // steps of 64 entries
@@ -1619,7 +1693,7 @@ __device__ __forceinline__ void eval_cams_gather_f(const int* __restrict__ cm_pt
       const int st = st0 + u;
       gather((st + DG) % R, (st + DG) % R, st + DG);
       load_idx((st + DI) % R, st + DI);
-      if (i0 + 64 * st < e) frame_rows_acc(xy[u], X[u], f, acc);
+      if (i0 + 64 * st < e) frame_rows_acc<LOSS>(xy[u], X[u], f, acc, lk);
     }
   }
 }
@@ -1807,7 +1881,7 @@ __device__ __forceinline__ void pipe_entries_uni(const int4* __restrict__ idx, c
 }
 
 // UNI: the chunks of `list` are uniform (chunk_uni), tables read once per block
-template <bool UNI>
+template <bool UNI, int LOSS = DAB_LOSS_TRIVIAL>
 __global__ __launch_bounds__(256) void k_eval_cams(DevView v, const int* __restrict__ chunk_beg,
                                                    const int* __restrict__ list,
                                                    const double* __restrict__ points,
@@ -1821,14 +1895,14 @@ __global__ __launch_bounds__(256) void k_eval_cams(DevView v, const int* __restr
   for (int i = 0; i < 27; ++i) acc[i] = 0.0;
   if constexpr (UNI) {
     const int2 u = v.chunk_uni[c];
-    eval_cams_uni_pipe(v, b + threadIdx.x, e, blockDim.x, points, [&]() { return UniTabs(ext, v.intr, u.x, u.y); },
-                       acc);
+    eval_cams_uni_pipe<3, LOSS>(v, b + threadIdx.x, e, blockDim.x, points,
+                                [&]() { return UniTabs(ext, v.intr, u.x, u.y); }, acc);
   } else if (small_tabs_fit(v.E, v.NI)) {
     extern __shared__ double tabs_lds[];
-    eval_cams_chunk(v, b + threadIdx.x, e, blockDim.x, points, stage_small_tabs(tabs_lds, v.E, v.NI, camtab, v.intr),
-                    acc);
+    eval_cams_chunk<LOSS>(v, b + threadIdx.x, e, blockDim.x, points,
+                          stage_small_tabs(tabs_lds, v.E, v.NI, camtab, v.intr), acc);
   } else {
-    eval_cams_chunk(v, b + threadIdx.x, e, blockDim.x, points, GlobalTabs{camtab, v.intr}, acc);
+    eval_cams_chunk<LOSS>(v, b + threadIdx.x, e, blockDim.x, points, GlobalTabs{camtab, v.intr}, acc);
   }
   // per-wave transposed sums (wave_sums_transposed), then the waves in order
   __shared__ double wsum[kRedBlock / 64][27];
@@ -1845,12 +1919,12 @@ __global__ __launch_bounds__(256) void k_eval_cams(DevView v, const int* __restr
 void launch_eval_cams(hipStream_t s, const DevView& v, const ChunkLists& cl, const int* chunk_beg,
                       const double* points, const double* ext, const double* camtab, double* partial) {
   if (cl.nuni > 0)
-    k_eval_cams<true><<<cl.nuni, 256, 0, s>>>(v, chunk_beg, cl.nuni == cl.nchunk ? nullptr : cl.uni, points, ext,
-                                              camtab, partial);
+    DAB_LOSS_SWITCH(v.loss, k_eval_cams<true, LOSS><<<cl.nuni, 256, 0, s>>>(
+                                v, chunk_beg, cl.nuni == cl.nchunk ? nullptr : cl.uni, points, ext, camtab, partial));
   if (cl.ngen > 0) {
     const size_t lds = small_tabs_fit(v.E, v.NI) ? small_tabs_bytes(v.E, v.NI) : 0;
-    k_eval_cams<false><<<cl.ngen, 256, lds, s>>>(v, chunk_beg, cl.ngen == cl.nchunk ? nullptr : cl.gen, points,
-                                                 ext, camtab, partial);
+    DAB_LOSS_SWITCH(v.loss, k_eval_cams<false, LOSS><<<cl.ngen, 256, lds, s>>>(
+                                v, chunk_beg, cl.ngen == cl.nchunk ? nullptr : cl.gen, points, ext, camtab, partial));
   }
 }
 
@@ -1936,7 +2010,7 @@ __device__ __forceinline__ void lds_wait_ge(const unsigned* w, unsigned want, un
 // C2: 8, 8), 0: the run-time wpc_rt, wps_rt. Round 6: the constants fold the part cuts'
 // divisions, the part-combine and slice-part loops and the slot arithmetic — C2 9.29 ->
 // 8.44 us per launch, C3 unchanged, bitwise the same sums (profiles/r06zk_*)
-template <int WPC_, int WPS_>
+template <int WPC_, int WPS_, int LOSS = DAB_LOSS_TRIVIAL>
 __global__ __launch_bounds__(1024) void k_eval_bal(DevView v, const int* __restrict__ chunk_beg,
                                                    const double* __restrict__ points, const double* __restrict__ ext,
                                                    const double* __restrict__ camtab, double* __restrict__ V,
@@ -1945,6 +2019,7 @@ __global__ __launch_bounds__(1024) void k_eval_bal(DevView v, const int* __restr
                                                    unsigned long long* __restrict__ fx_next, unsigned* __restrict__ err,
                                                    int wpc_rt, int wps_rt, int side) {
   const int wpc = WPC_ > 0 ? WPC_ : wpc_rt, wps = WPS_ > 0 ? WPS_ : wps_rt;
+  const LossK lk = loss_of(v);
   __shared__ double rt_s[kLdsCams * 12];
   __shared__ double k_s[kLdsCams * 6];
   __shared__ double csum[kBalCW][27];            // camera waves' sums: [slot * wpc + part]
@@ -2039,14 +2114,14 @@ __global__ __launch_bounds__(1024) void k_eval_bal(DevView v, const int* __restr
 #pragma unroll
     for (int i = 0; i < 27; ++i) acc[i] = 0.0;
     const double* fr = cfr[slot];
-    eval_cams_gather_f(v.cm_pt, v.cm_xy, points, lo + lane, hi, acc, [&]() {
+    eval_cams_gather_f<LOSS>(v.cm_pt, v.cm_xy, points, lo + lane, hi, acc, [&]() {
       // the frames, built while the first gathers fly (kSideTestTimeout, a test: a frame flag
       // that never comes — the wait must run out and fail the pass closed)
       if (!abl_no_frames) lds_wait_ge(&tbar, test_timeout ? 2u : 1u, err, costfx, 1u);
       const UniFrame f(UniFrame::FromShared{}, fr);
       DAB_STAMP(1);
       return f;
-    });
+    }, lk);
     DAB_STAMP(2);
     wave_sums_transposed<27>(acc, csum[slot * wpc + part]);
     unsigned old = 0;
@@ -2194,9 +2269,10 @@ __global__ __launch_bounds__(1024) void k_eval_bal(DevView v, const int* __restr
         qxy[d] = v.obs_xy[off + 64 * kn + lane];
         if (k >= len) continue;  // wave-uniform; no load below
         const bool live = id.x >= 0;
-        double ru, rv, jx0[3], jx1[3];
-        obs_rows<true, -1, LdsTabs<true, false>, false>(id, xy, X, tabs, ru, rv, jx0, jx1, nullptr, nullptr);
+        double ru, rv, jx0[3], jx1[3], rho = 0.0;
+        obs_rows_l<LOSS, true, -1, false>(lk, rho, id, xy, X, tabs, ru, rv, jx0, jx1, nullptr, nullptr);
         if (!live) ru = rv = jx0[0] = jx0[1] = jx0[2] = jx1[0] = jx1[1] = jx1[2] = 0.0;
+        if constexpr (LOSS != DAB_LOSS_TRIVIAL) rho = live ? rho : 0.0;
         c[0] = fma(jx1[0], jx1[0], fma(jx0[0], jx0[0], c[0]));
         c[1] = fma(jx1[0], jx1[1], fma(jx0[0], jx0[1], c[1]));
         c[2] = fma(jx1[0], jx1[2], fma(jx0[0], jx0[2], c[2]));
@@ -2208,7 +2284,8 @@ __global__ __launch_bounds__(1024) void k_eval_bal(DevView v, const int* __restr
         c[8] = fma(jx1[2], rv, fma(jx0[2], ru, c[8]));
         // a non-finite residual makes the lane's r^2 sum non-finite, which the
         // fixed-point add below flags: no per-row finiteness test
-        acc[0] = fma(rv, rv, fma(ru, ru, acc[0]));
+        if constexpr (LOSS == DAB_LOSS_TRIVIAL) acc[0] = fma(rv, rv, fma(ru, ru, acc[0]));
+        else acc[0] += rho;
       }
     }
     const int p = 64 * sl + lane;
@@ -2267,14 +2344,17 @@ void launch_eval_bal(hipStream_t s, const DevView& v, const int* chunk_beg, cons
                      const double* camtab, double* V, double* g, double* ug, unsigned long long* costfx,
                      unsigned long long* fx_next, unsigned* err, int grid, int side) {
   const int wpc = fused_wpc(v.NC, grid), wps = fused_wps(v.nslice, v.E, grid);
-  if (wpc == 2 && wps == 1)
-    k_eval_bal<2, 1><<<grid, 1024, 0, s>>>(v, chunk_beg, points, ext, camtab, V, g, ug, costfx, fx_next, err, wpc, wps, side);
-  else if (wpc == 8 && wps == 8)
-    k_eval_bal<8, 8><<<grid, 1024, 0, s>>>(v, chunk_beg, points, ext, camtab, V, g, ug, costfx, fx_next, err, wpc, wps, side);
-  else
-    k_eval_bal<0, 0><<<grid, 1024, 0, s>>>(v, chunk_beg, points, ext, camtab, V, g, ug, costfx, fx_next, err, wpc, wps, side);
+  DAB_LOSS_SWITCH(v.loss, {
+    if (wpc == 2 && wps == 1)
+      k_eval_bal<2, 1, LOSS><<<grid, 1024, 0, s>>>(v, chunk_beg, points, ext, camtab, V, g, ug, costfx, fx_next, err, wpc, wps, side);
+    else if (wpc == 8 && wps == 8)
+      k_eval_bal<8, 8, LOSS><<<grid, 1024, 0, s>>>(v, chunk_beg, points, ext, camtab, V, g, ug, costfx, fx_next, err, wpc, wps, side);
+    else
+      k_eval_bal<0, 0, LOSS><<<grid, 1024, 0, s>>>(v, chunk_beg, points, ext, camtab, V, g, ug, costfx, fx_next, err, wpc, wps, side);
+  });
 }
 
+template <int LOSS>
 __global__ __launch_bounds__(256) void k_eval_cross(DevView v, const int* __restrict__ chunk_beg,
                                                     const int4* __restrict__ x_idx,
                                                     const double2* __restrict__ x_xy,
@@ -2288,12 +2368,13 @@ __global__ __launch_bounds__(256) void k_eval_cross(DevView v, const int* __rest
   for (int i = 0; i < 36; ++i) acc[i] = 0.0;
   extern __shared__ double tabs_lds[];
   const bool small = small_tabs_fit(v.E, v.NI);
+  const LossK lk = loss_of(v);
   SmallTabs st{nullptr, nullptr};
   if (small) st = stage_small_tabs(tabs_lds, v.E, v.NI, camtab, v.intr);
   // both slots' camera rows (no d r / d X), Jc0^T Jc1 accumulated
   auto body = [&](const int4 id, const double2 xy, const double (&X)[3], const auto& tabs) {
-    double ru, rv, ja[6], jb[6], da[6], db[6];
-    obs_rows<false, 2>(id, xy, X, tabs, ru, rv, nullptr, nullptr, ja, jb, da, db);
+    double ru, rv, ja[6], jb[6], da[6], db[6], rho;
+    obs_rows_l<LOSS, false, 2>(lk, rho, id, xy, X, tabs, ru, rv, nullptr, nullptr, ja, jb, da, db);
 #pragma unroll
     for (int a = 0; a < 6; ++a)
 #pragma unroll
@@ -2323,7 +2404,7 @@ __global__ __launch_bounds__(256) void k_eval_cross(DevView v, const int* __rest
                      Z1[k] = sr ? X[k] : Q[k] - Tb[9 + k];
                    }
                    Proj pr;
-                   project(P, Kr, xy.x, xy.y, pr, true);
+                   project<LOSS>(P, Kr, xy.x, xy.y, pr, true, lk);  // w0 and w1 each carry sqrt(rho')
 #pragma unroll
                    for (int row = 0; row < 2; ++row) {
                      const double* A = row == 0 ? pr.A0 : pr.A1;
@@ -2404,7 +2485,7 @@ __global__ __launch_bounds__(256) void k_eval_cross(DevView v, const int* __rest
 // sums). It replaces, for these observations, both camera-major entries and the separate
 // cross pass: one 56-B input per observation instead of three. k_cam_final adds the
 // camera halves to the camera-major partials of the remaining entries.
-template <int PNS, int PGD, bool UT = false>
+template <int PNS, int PGD, bool UT = false, int LOSS = DAB_LOSS_TRIVIAL>
 __global__ __launch_bounds__(256) void k_eval_pair(DevView v, const int* __restrict__ chunk_beg,
                                                    const int4* __restrict__ x_idx,
                                                    const double2* __restrict__ x_xy,
@@ -2424,6 +2505,7 @@ __global__ __launch_bounds__(256) void k_eval_pair(DevView v, const int* __restr
     return;
   }
   const int4 id0 = x_idx[b];
+  const LossK lk = loss_of(v);
   bool sa, sr;
   ext_frame(camtab, id0.y, jl[0], threadIdx.x, sa);
   ext_frame(camtab, id0.z, jl[1], threadIdx.x, sr);
@@ -2463,7 +2545,8 @@ __global__ __launch_bounds__(256) void k_eval_pair(DevView v, const int* __restr
                    Z1[k] = sr ? X[k] : Q[k] - Tb[9 + k];
                  }
                  Proj pr;
-                 project(P, Kr, xy.x, xy.y, pr, true);
+                 // w0, w1 and r are linear in (A, r) of the observation: scaled before the sums
+                 project<LOSS>(P, Kr, xy.x, xy.y, pr, true, lk);
                  if (!valid) {  // a lane past the chunk's end: zero rows add exactly nothing
                    pr.ru = pr.rv = 0.0;
 #pragma unroll
@@ -2563,11 +2646,13 @@ void launch_eval_pair(hipStream_t s, const DevView& v, int nchunk, const int* ch
   // 5 slots 212 against 198 at C5 before the chunk cut below). With one intrinsic per pair
   // the chunk's arc, ring and intrinsic tables are uniform values (no LDS tables): 198
   // against 244 us.
-  if (uni_intr)
-    k_eval_pair<4, 1, true><<<nchunk, 256, 0, s>>>(v, chunk_beg, x_idx, x_xy, points, camtab, xpart, cpart);
-  else
-    k_eval_pair<4, 1, false><<<nchunk, 256, small_tabs_bytes(v.E, v.NI), s>>>(v, chunk_beg, x_idx, x_xy, points,
-                                                                            camtab, xpart, cpart);
+  DAB_LOSS_SWITCH(v.loss, {
+    if (uni_intr)
+      k_eval_pair<4, 1, true, LOSS><<<nchunk, 256, 0, s>>>(v, chunk_beg, x_idx, x_xy, points, camtab, xpart, cpart);
+    else
+      k_eval_pair<4, 1, false, LOSS><<<nchunk, 256, small_tabs_bytes(v.E, v.NI), s>>>(v, chunk_beg, x_idx, x_xy,
+                                                                                      points, camtab, xpart, cpart);
+  });
 }
 
 // ug[c] = its camera-major chunk partials (seg_chunk) + its halves of the pair chunks
@@ -2612,14 +2697,16 @@ void launch_eval_cams_gen(hipStream_t s, const DevView& v, int nchunk, const int
                           const double* ext, const double* camtab, double* partial) {
   if (nchunk <= 0) return;
   const size_t lds = small_tabs_fit(v.E, v.NI) ? small_tabs_bytes(v.E, v.NI) : 0;
-  k_eval_cams<false><<<nchunk, 256, lds, s>>>(v, chunk_beg, nullptr, points, ext, camtab, partial);
+  DAB_LOSS_SWITCH(v.loss, k_eval_cams<false, LOSS><<<nchunk, 256, lds, s>>>(v, chunk_beg, nullptr, points, ext, camtab,
+                                                                           partial));
 }
 
 void launch_eval_cross(hipStream_t s, const DevView& v, int nchunk, const int* chunk_beg, const int4* x_idx,
                        const double2* x_xy, const double* points, const double* camtab, double* partial) {
   if (nchunk <= 0) return;
   const size_t lds = small_tabs_fit(v.E, v.NI) ? small_tabs_bytes(v.E, v.NI) : 0;
-  k_eval_cross<<<nchunk, 256, lds, s>>>(v, chunk_beg, x_idx, x_xy, points, camtab, partial);
+  DAB_LOSS_SWITCH(v.loss,
+                  k_eval_cross<LOSS><<<nchunk, 256, lds, s>>>(v, chunk_beg, x_idx, x_xy, points, camtab, partial));
 }
 
 // ------------------------------------------------------------------------------------
@@ -2702,7 +2789,7 @@ __device__ __forceinline__ void make_y(const double (&ja)[6], const double (&jb)
 }
 
 // SMALL: the camera tables are staged in LDS (small_tabs_fit) and the grid strides
-template <class YT, bool SMALL, bool REC = false>  // REC: [NE][18] records instead of planes
+template <class YT, bool SMALL, bool REC = false, int LOSS = DAB_LOSS_TRIVIAL>  // REC: [NE][18] records instead of planes
 __global__ __launch_bounds__(256) void k_entry_y(DevView v, const double* __restrict__ points,
                                                  const double* __restrict__ camtab,
                                                  const double* __restrict__ scc,
@@ -2717,13 +2804,15 @@ __global__ __launch_bounds__(256) void k_entry_y(DevView v, const double* __rest
     const int c = v.ext_col[slot1 ? id.z : id.y];
     const double2 xy = v.cm_xy[i];
     const double X[3] = {points[3 * (size_t)id.x], points[3 * (size_t)id.x + 1], points[3 * (size_t)id.x + 2]};
-    double ru, rv, jx0[3], jx1[3], ja[6], jb[6];
+    // under a loss both factors of Jc^T Jp carry sqrt(rho'): Y is that of the scaled rows
+    const LossK lk = loss_of(v);
+    double ru, rv, jx0[3], jx1[3], ja[6], jb[6], rho;
     if constexpr (SMALL) {
-      if (slot1) obs_rows<true, 1>(id, xy, X, st, ru, rv, jx0, jx1, ja, jb);
-      else obs_rows<true, 0>(id, xy, X, st, ru, rv, jx0, jx1, ja, jb);
+      if (slot1) obs_rows_l<LOSS, true, 1>(lk, rho, id, xy, X, st, ru, rv, jx0, jx1, ja, jb);
+      else obs_rows_l<LOSS, true, 0>(lk, rho, id, xy, X, st, ru, rv, jx0, jx1, ja, jb);
     } else {
-      if (slot1) obs_rows<true, 1>(id, xy, X, GlobalTabs{camtab, v.intr}, ru, rv, jx0, jx1, ja, jb);
-      else obs_rows<true, 0>(id, xy, X, GlobalTabs{camtab, v.intr}, ru, rv, jx0, jx1, ja, jb);
+      if (slot1) obs_rows_l<LOSS, true, 1>(lk, rho, id, xy, X, GlobalTabs{camtab, v.intr}, ru, rv, jx0, jx1, ja, jb);
+      else obs_rows_l<LOSS, true, 0>(lk, rho, id, xy, X, GlobalTabs{camtab, v.intr}, ru, rv, jx0, jx1, ja, jb);
     }
     double y[18];
     make_y(ja, jb, jx0, jx1, scc + 6 * c, PU + 6 * (size_t)id.x, y);
@@ -2737,7 +2826,7 @@ __global__ __launch_bounds__(256) void k_entry_y(DevView v, const double* __rest
   }
 }
 
-template <class YT, bool SMALL>
+template <class YT, bool SMALL, int LOSS = DAB_LOSS_TRIVIAL>
 __global__ __launch_bounds__(256) void k_entry_y_slots(DevView v, const double* __restrict__ points,
                                                        const double* __restrict__ camtab,
                                                        const double* __restrict__ scc,
@@ -2752,9 +2841,12 @@ __global__ __launch_bounds__(256) void k_entry_y_slots(DevView v, const double* 
     const int c0 = v.ext_col[id.y], c1 = id.z >= 0 ? v.ext_col[id.z] : -1;
     if (c0 < 0 && c1 < 0) continue;
     const double X[3] = {points[3 * (size_t)id.x], points[3 * (size_t)id.x + 1], points[3 * (size_t)id.x + 2]};
-    double ru, rv, jx0[3], jx1[3], ja[6], jb[6], da[6], db[6];
-    if constexpr (SMALL) obs_rows<true, 2>(id, v.obs_xy[s], X, st, ru, rv, jx0, jx1, ja, jb, da, db);
-    else obs_rows<true, 2>(id, v.obs_xy[s], X, GlobalTabs{camtab, v.intr}, ru, rv, jx0, jx1, ja, jb, da, db);
+    const LossK lk = loss_of(v);
+    double ru, rv, jx0[3], jx1[3], ja[6], jb[6], da[6], db[6], rho;
+    if constexpr (SMALL) obs_rows_l<LOSS, true, 2>(lk, rho, id, v.obs_xy[s], X, st, ru, rv, jx0, jx1, ja, jb, da, db);
+    else
+      obs_rows_l<LOSS, true, 2>(lk, rho, id, v.obs_xy[s], X, GlobalTabs{camtab, v.intr}, ru, rv, jx0, jx1, ja, jb, da,
+                                db);
     const double* pu = PU + 6 * (size_t)id.x;
     double y[18];
     if (c0 >= 0) {
@@ -2768,17 +2860,17 @@ __global__ __launch_bounds__(256) void k_entry_y_slots(DevView v, const double* 
   }
 }
 
-template <class YT>
+template <class YT, int LOSS>
 static void launch_entry_y_t(hipStream_t s, const DevView& v, const double* points, const double* camtab,
                              const double* scale_c, const double* PU, YT* cm, YT* pm) {
   const int g = grid_for(v.NE, 256, 1 << 20), gs = grid_for(v.N, 256, 1 << 20);
   if (small_tabs_fit(v.E, v.NI)) {
     const size_t lds = small_tabs_bytes(v.E, v.NI);
-    if (cm) k_entry_y<YT, true><<<std::min(g, kSmallGrid), 256, lds, s>>>(v, points, camtab, scale_c, PU, cm);
-    if (pm) k_entry_y_slots<YT, true><<<std::min(gs, kSmallGrid), 256, lds, s>>>(v, points, camtab, scale_c, PU, pm);
+    if (cm) k_entry_y<YT, true, false, LOSS><<<std::min(g, kSmallGrid), 256, lds, s>>>(v, points, camtab, scale_c, PU, cm);
+    if (pm) k_entry_y_slots<YT, true, LOSS><<<std::min(gs, kSmallGrid), 256, lds, s>>>(v, points, camtab, scale_c, PU, pm);
   } else {
-    if (cm) k_entry_y<YT, false><<<g, 256, 0, s>>>(v, points, camtab, scale_c, PU, cm);
-    if (pm) k_entry_y_slots<YT, false><<<gs, 256, 0, s>>>(v, points, camtab, scale_c, PU, pm);
+    if (cm) k_entry_y<YT, false, false, LOSS><<<g, 256, 0, s>>>(v, points, camtab, scale_c, PU, cm);
+    if (pm) k_entry_y_slots<YT, false, LOSS><<<gs, 256, 0, s>>>(v, points, camtab, scale_c, PU, pm);
   }
 }
 
@@ -2787,16 +2879,23 @@ void launch_entry_y(hipStream_t s, const DevView& v, const double* points, const
   if (v.NE <= 0) return;
   if (rec && !Y.f32) {  // records for the explicit S blocks; the slot planes as usual
     const int g = grid_for(v.NE, 256, 1 << 20);
-    if (small_tabs_fit(v.E, v.NI))
-      k_entry_y<double, true, true><<<std::min(g, kSmallGrid), 256, small_tabs_bytes(v.E, v.NI), s>>>(
-          v, points, camtab, scale_c, PU, rec);
-    else
-      k_entry_y<double, false, true><<<g, 256, 0, s>>>(v, points, camtab, scale_c, PU, rec);
-    if (with_pm) launch_entry_y_t<double>(s, v, points, camtab, scale_c, PU, nullptr, (double*)Y.pm);
+    DAB_LOSS_SWITCH(v.loss, {
+      if (small_tabs_fit(v.E, v.NI))
+        k_entry_y<double, true, true, LOSS><<<std::min(g, kSmallGrid), 256, small_tabs_bytes(v.E, v.NI), s>>>(
+            v, points, camtab, scale_c, PU, rec);
+      else
+        k_entry_y<double, false, true, LOSS><<<g, 256, 0, s>>>(v, points, camtab, scale_c, PU, rec);
+      if (with_pm) launch_entry_y_t<double, LOSS>(s, v, points, camtab, scale_c, PU, nullptr, (double*)Y.pm);
+    });
     return;
   }
-  if (Y.f32) launch_entry_y_t<float>(s, v, points, camtab, scale_c, PU, (float*)Y.cm, with_pm ? (float*)Y.pm : nullptr);
-  else launch_entry_y_t<double>(s, v, points, camtab, scale_c, PU, (double*)Y.cm, with_pm ? (double*)Y.pm : nullptr);
+  // fp32 records (pcg_fp32) exist for the TRIVIAL loss only: dab_solve refuses the combination
+  if (Y.f32)
+    launch_entry_y_t<float, DAB_LOSS_TRIVIAL>(s, v, points, camtab, scale_c, PU, (float*)Y.cm,
+                                              with_pm ? (float*)Y.pm : nullptr);
+  else
+    DAB_LOSS_SWITCH(v.loss, launch_entry_y_t<double, LOSS>(s, v, points, camtab, scale_c, PU, (double*)Y.cm,
+                                                           with_pm ? (double*)Y.pm : nullptr));
 }
 
 // one wave per S block; lane (a,b) < 36 accumulates -sum Y_row[a,:] . Y_col[b,:]
@@ -3038,6 +3137,7 @@ int schur_tile_batch_cap(int NC, bool single) {
 
 // k_schur_y: thread per record; tables staged in LDS; rhs partials of the work-group in LDS
 // (fixed point, 2^(60 - kx[R] - kq) units), then one global integer atomic per rhs row.
+template <int LOSS>
 __global__ __launch_bounds__(256, 3) void k_schur_y(DevView v, const double* __restrict__ points,
                                                  const double* __restrict__ camtab, const double* __restrict__ PU,
                                                  const double* __restrict__ q, const double* __restrict__ scc,
@@ -3082,10 +3182,13 @@ __global__ __launch_bounds__(256, 3) void k_schur_y(DevView v, const double* __r
         os = a.sch_ent[e].x;
         id = v.obs_idx[os >> 1];
       }
-      const double2 xy0 = make_double2(0.0, 0.0);  // the residual is not used
-      double ru, rv, jx0[3], jx1[3], ja[6], jb[6];  // the rows of the record's camera slot only
-      if (os & 1) obs_rows<true, 1>(id, xy0, X, st, ru, rv, jx0, jx1, ja, jb);
-      else obs_rows<true, 0>(id, xy0, X, st, ru, rv, jx0, jx1, ja, jb);
+      double2 xy0 = make_double2(0.0, 0.0);  // the residual is not used ...
+      // ... except by a loss: its weight needs the entry's pixel (16 B more per entry)
+      if constexpr (LOSS != DAB_LOSS_TRIVIAL) xy0 = v.obs_xy[os >> 1];
+      const LossK lk = loss_of(v);
+      double ru, rv, jx0[3], jx1[3], ja[6], jb[6], rho;  // the rows of the record's camera slot only
+      if (os & 1) obs_rows_l<LOSS, true, 1>(lk, rho, id, xy0, X, st, ru, rv, jx0, jx1, ja, jb);
+      else obs_rows_l<LOSS, true, 0>(lk, rho, id, xy0, X, st, ru, rv, jx0, jx1, ja, jb);
 #pragma unroll
       for (int r = 0; r < 6; ++r)
 #pragma unroll
@@ -3353,8 +3456,8 @@ void launch_schur_y(hipStream_t s, const DevView& v, const double* points, const
   if (a.nrec <= 0) return;
   const size_t lds = small_tabs_bytes(v.E, v.NI) + sizeof(unsigned long long) * 6 * (size_t)v.NC +
                      sizeof(double) * 4 * 32 * 18;  // + a half-wave record stage per wave
-  k_schur_y<<<std::min(grid_for(a.nrec, 256, 1 << 20), kSmallGrid), 256, lds, s>>>(v, points, camtab, PU, q, scale_c,
-                                                                                   a, yrec, rhs_out);
+  DAB_LOSS_SWITCH(v.loss, k_schur_y<LOSS><<<std::min(grid_for(a.nrec, 256, 1 << 20), kSmallGrid), 256, lds, s>>>(
+                              v, points, camtab, PU, q, scale_c, a, yrec, rhs_out));
 }
 void launch_schur_tiles(hipStream_t s, const double* yrec, const SchurTiles& a, int NC) {
   static bool attr = false;
@@ -3476,7 +3579,7 @@ static size_t mf2_lds_bytes(int E, int NI, int NC, bool product) {
                            (product ? (kMfBlock / 64) * 6 * (size_t)(NC | 1) : 0)) +
          2 * sizeof(int) * (size_t)E;
 }
-template <int MODE>
+template <int MODE, int LOSS = DAB_LOSS_TRIVIAL>
 __global__ __launch_bounds__(kMfBlock, 4) void k_mf_frame(DevView v, const double* __restrict__ points,
                                                        const double* __restrict__ camtab,
                                                        const double* __restrict__ scc,
@@ -3596,7 +3699,8 @@ __global__ __launch_bounds__(kMfBlock, 4) void k_mf_frame(DevView v, const doubl
 #pragma unroll
     for (int k = 0; k < 3; ++k) Z0[k] = sa ? Q[k] : P[k] - Ta[9 + k];
     Proj pr;
-    project(P, Kr, xy.x, xy.y, pr, true);
+    // every product below is A^T A applied to a vector: the two scaled factors give rho'
+    project<LOSS>(P, Kr, xy.x, xy.y, pr, true, loss_of(v));
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       A0[k] = pr.A0[k];
@@ -4033,6 +4137,9 @@ __global__ __launch_bounds__(kMfBlock, 4) void k_mf_frame32(DevView v, const dou
 // the loop sums Y~ Y~^T and Y~ q (27) in the frame, and the chunk's J_l and s_c are applied
 // once to the sums (cam_frame_entry). Per entry only R, t (and K) from LDS: no Rd | Jd rows,
 // no per-row J_d products, and no s_c in the loop.
+// Under a loss the weight needs the residual: the entry's pixel (cm_xy, 16 B per entry) is
+// loaded in the non-trivial instantiations only; w and j_p each carry sqrt(rho').
+template <int LOSS>
 __global__ __launch_bounds__(256) void k_mf_diag_frame(DevView v, int nchunk, const int* __restrict__ run_beg,
                                                        const int4* __restrict__ run_rec,
                                                        const double* __restrict__ points,
@@ -4118,7 +4225,12 @@ __global__ __launch_bounds__(256) void k_mf_diag_frame(DevView v, int nchunk, co
 #pragma unroll
         for (int t = 0; t < 3; ++t) Z[t] = slot1 ? Zb[t] : (sa ? Qp[t] : P[t] - Ta[9 + t]);
         Proj pr;
-        project(P, Kr, 0.0, 0.0, pr, true);
+        if constexpr (LOSS == DAB_LOSS_TRIVIAL) {
+          project(P, Kr, 0.0, 0.0, pr, true);
+        } else {
+          const double2 xy = v.cm_xy[i + j];
+          project<LOSS>(P, Kr, xy.x, xy.y, pr, true, loss_of(v));
+        }
 #pragma unroll
         for (int row = 0; row < 2; ++row) {
           const double* a = row == 0 ? pr.A0 : pr.A1;
@@ -4194,8 +4306,8 @@ int mf_grid(int NP, int ncu) { return std::max(1, std::min((NP + kMfBlock - 1) /
 void launch_mf_product(hipStream_t s, const DevView& v, const double* points, const double* camtab,
                        const double* scale_c, const double* PU, const double* vec, double* partial, double* w,
                        int grid, const PcgState* st) {
-  k_mf_frame<0><<<grid, kMfBlock, mf2_lds_bytes(v.E, v.NI, v.NC, true), s>>>(v, points, camtab, scale_c, PU, vec,
-                                                                            nullptr, partial, st);
+  DAB_LOSS_SWITCH(v.loss, k_mf_frame<0, LOSS><<<grid, kMfBlock, mf2_lds_bytes(v.E, v.NI, v.NC, true), s>>>(
+                              v, points, camtab, scale_c, PU, vec, nullptr, partial, st));
   if (w) launch_pcg_fused_final(s, grid, 6 * v.NC, partial, w, st);
 }
 void launch_mf_product32(hipStream_t s, const DevView& v, const double* points, const double* camtab,
@@ -4208,8 +4320,8 @@ void launch_mf_product32(hipStream_t s, const DevView& v, const double* points, 
 void launch_mf_backsub(hipStream_t s, const DevView& v, const double* points, const double* camtab,
                        const double* scale_c, const double* PU, const double* q, const double* yc, double* dp,
                        int grid) {
-  k_mf_frame<1><<<grid, kMfBlock, mf2_lds_bytes(v.E, v.NI, v.NC, false), s>>>(v, points, camtab, scale_c, PU, yc, q,
-                                                                             dp, nullptr);
+  DAB_LOSS_SWITCH(v.loss, k_mf_frame<1, LOSS><<<grid, kMfBlock, mf2_lds_bytes(v.E, v.NI, v.NC, false), s>>>(
+                              v, points, camtab, scale_c, PU, yc, q, dp, nullptr));
 }
 void launch_mf_diag_rhs(hipStream_t s, const DevView& v, int nchunk, const int* run_beg, const int4* run_rec,
                         const double* points, const double* camtab, const double* scale_c, const double* PU,
@@ -4219,8 +4331,8 @@ void launch_mf_diag_rhs(hipStream_t s, const DevView& v, int nchunk, const int* 
   // NC <= E, so 14 E + 6 NI + 9 NC doubles stay below the 30 E + 6 NI of small_tabs_fit)
   const size_t lds =
       sizeof(double) * (kRtStride * (size_t)v.E + 6 * (size_t)v.NI + 9 * (size_t)v.NC) + sizeof(int) * (size_t)v.E;
-  k_mf_diag_frame<<<std::min(nchunk, kSmallGrid), 256, lds, s>>>(v, nchunk, run_beg, run_rec, points, camtab, scale_c,
-                                                                 PU, q, partial);
+  DAB_LOSS_SWITCH(v.loss, k_mf_diag_frame<LOSS><<<std::min(nchunk, kSmallGrid), 256, lds, s>>>(
+                              v, nchunk, run_beg, run_rec, points, camtab, scale_c, PU, q, partial));
 }
 
 void launch_backsub(hipStream_t s, const DevView& v, const double* PU, const double* q, YBufs Y,
@@ -4278,7 +4390,8 @@ void launch_cam_candidate(hipStream_t s, int E, const int* ext_col, const double
 // Model cost change -(J delta).(r + J delta / 2) and the candidate residual at x + delta
 // in one observation pass; J and r at x are re-evaluated (bitwise what the evaluation
 // pass saw), the candidate point is formed as x + delta exactly as k_axpy_points does.
-template <bool SMALL>
+// Under a loss: m and r are those of the scaled rows, and the candidate's term is rho(s_c).
+template <bool SMALL, int LOSS = DAB_LOSS_TRIVIAL>
 __global__ __launch_bounds__(256) void k_candidate(DevView v, const double* __restrict__ points,
                                                    const double* __restrict__ camtab,
                                                    const double* __restrict__ dp,
@@ -4306,8 +4419,8 @@ __global__ __launch_bounds__(256) void k_candidate(DevView v, const double* __re
     double m0 = 0.0, m1 = 0.0, ru, rv;
     {
       ObsJac o;
-      if constexpr (SMALL) obs_jacobian_t(id, xy, X, st, o);
-      else obs_jacobian(id, xy, X, camtab, v.intr, o);
+      if constexpr (SMALL) obs_jacobian_t<LOSS>(id, xy, X, st, o, loss_of(v));
+      else obs_jacobian_t<LOSS>(id, xy, X, GlobalTabs{camtab, v.intr}, o, loss_of(v));
       ru = o.pr.ru;
       rv = o.pr.rv;
 #pragma unroll
@@ -4366,8 +4479,9 @@ __global__ __launch_bounds__(256) void k_candidate(DevView v, const double* __re
       matvec_add(T0, Xc, T0 + 9, P);
     }
     Proj pc;
-    project(P, Kc, xy.x, xy.y, pc, false);
-    acc[1] += pc.ru * pc.ru + pc.rv * pc.rv;
+    project<LOSS>(P, Kc, xy.x, xy.y, pc, false, loss_of(v));
+    if constexpr (LOSS == DAB_LOSS_TRIVIAL) acc[1] += pc.ru * pc.ru + pc.rv * pc.rv;
+    else acc[1] += pc.rho;
     acc[2] += (isfinite(pc.ru) && isfinite(pc.rv)) ? 0.0 : 1.0;
   }
   block_reduce_store<3>(acc, partial + 3 * (size_t)blockIdx.x);
@@ -4378,6 +4492,7 @@ __global__ __launch_bounds__(256) void k_candidate(DevView v, const double* __re
 // w~ = J_l dw once per camera, instead of building every row of the observation; the
 // candidate residual as k_candidate. LDS: R, t at x | R, t at x + delta | K | small-angle
 // flags | [w~ | dt] per camera.
+template <int LOSS>
 __global__ __launch_bounds__(256) void k_candidate_frame(DevView v, const double* __restrict__ points,
                                                          const double* __restrict__ camtab,
                                                          const double* __restrict__ dp,
@@ -4483,7 +4598,7 @@ __global__ __launch_bounds__(256) void k_candidate_frame(DevView v, const double
         for (int k = 0; k < 3; ++k) dP[k] += d[3 + k] - cz[k];
       }
       Proj pr;
-      project(P, Kr, xy.x, xy.y, pr, true);
+      project<LOSS>(P, Kr, xy.x, xy.y, pr, true, loss_of(v));
       ru = pr.ru;
       rv = pr.rv;
       m0 = pr.A0[0] * dP[0] + pr.A0[1] * dP[1] + pr.A0[2] * dP[2];
@@ -4504,8 +4619,9 @@ __global__ __launch_bounds__(256) void k_candidate_frame(DevView v, const double
       matvec_add(T0, Xc, T0 + 9, P);
     }
     Proj pc;
-    project(P, Kr, xy.x, xy.y, pc, false);
-    acc[1] += pc.ru * pc.ru + pc.rv * pc.rv;
+    project<LOSS>(P, Kr, xy.x, xy.y, pc, false, loss_of(v));
+    if constexpr (LOSS == DAB_LOSS_TRIVIAL) acc[1] += pc.ru * pc.ru + pc.rv * pc.rv;
+    else acc[1] += pc.rho;
     acc[2] += (isfinite(pc.ru) && isfinite(pc.rv)) ? 0.0 : 1.0;
   }
   block_reduce_store<3>(acc, partial + 3 * (size_t)blockIdx.x);
@@ -4517,9 +4633,11 @@ void launch_candidate(hipStream_t s, const DevView& v, const double* points, con
   if (small_tabs_fit(v.E, v.NI)) {
     const size_t lds = sizeof(double) * (2 * kRtStride * (size_t)v.E + 6 * (size_t)v.NI + 6 * (size_t)v.NC) +
                        sizeof(int) * (size_t)v.E;
-    k_candidate_frame<<<grid, 256, lds, s>>>(v, points, camtab, delta_p, delta_c, camtab_c, partial);
+    DAB_LOSS_SWITCH(v.loss, k_candidate_frame<LOSS><<<grid, 256, lds, s>>>(v, points, camtab, delta_p, delta_c,
+                                                                          camtab_c, partial));
   } else {
-    k_candidate<false><<<grid, 256, 0, s>>>(v, points, camtab, delta_p, delta_c, camtab_c, partial);
+    DAB_LOSS_SWITCH(v.loss, k_candidate<false, LOSS><<<grid, 256, 0, s>>>(v, points, camtab, delta_p, delta_c,
+                                                                         camtab_c, partial));
   }
 }
 

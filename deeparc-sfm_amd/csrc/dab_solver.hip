@@ -401,6 +401,9 @@ struct dab_handle {
   Dev setup_tmp{"set-up scratch"};  // the device set-up's scratch (released by the next set-up)
   Dev keep_dev{"kept buffers"};     // the Sticky buffers below (never released, re-sized by drop + alloc)
   DevView view{};
+  // robust loss (dab_set_loss): the type and a, b, c live in view (loss, loss_a..c), which
+  // set_problem fills field by field and so never resets; this is the scale as it was given
+  double loss_scale = 0.0;
   int4* d_obs_idx = nullptr;
   double2* d_obs_xy = nullptr;
   // fused pass: packed 4-B slot records of the point waves (DevView::obs_e)
@@ -3078,6 +3081,30 @@ extern "C" int dab_solve(dab_handle* h, const dab_options* opt_in, dab_summary* 
   CHECK_RC(guard_fail(h, "dab_solve"));
   return rc;
 }
+extern "C" int dab_set_loss(dab_handle* h, int32_t loss_type, double scale) {
+  clear_error();
+  if (!h) return set_error(DAB_E_INVALID, "null handle");
+  if (loss_type != DAB_LOSS_TRIVIAL && loss_type != DAB_LOSS_HUBER && loss_type != DAB_LOSS_SOFT_L1 &&
+      loss_type != DAB_LOSS_CAUCHY)
+    return set_error(DAB_E_INVALID, "unknown loss type");
+  if (loss_type == DAB_LOSS_TRIVIAL) scale = 1.0;  // ignored
+  if (!(std::isfinite(scale) && scale > 0.0)) return set_error(DAB_E_INVALID, "loss scale must be finite and > 0");
+  // launches copy the view by value: passes already enqueued keep the loss they were launched with
+  h->view.loss = loss_type;
+  h->view.loss_a = scale;
+  h->view.loss_b = scale * scale;
+  h->view.loss_c = 1.0 / h->view.loss_b;
+  h->loss_scale = scale;
+  return 0;
+}
+extern "C" int dab_get_loss(dab_handle* h, int32_t* loss_type, double* scale) {
+  clear_error();
+  if (!h) return set_error(DAB_E_INVALID, "null handle");
+  if (loss_type) *loss_type = h->view.loss;
+  if (scale) *scale = h->view.loss == DAB_LOSS_TRIVIAL ? 0.0 : h->loss_scale;
+  return 0;
+}
+
 static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum) {
   clear_error();
   if (!h || !h->have_problem) return set_error(DAB_E_STATE, "no problem set");
@@ -3085,6 +3112,10 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
   dab_options opt;
   if (opt_in) opt = *opt_in;
   else dab_options_init(&opt);
+  // the fp32 matrix-free product (proj_jac32) never forms a residual, and fp32 Y records from
+  // an fp32-weighted row are numerics work of their own: refused, never a silent fp64 fall-back
+  if (opt.pcg_fp32 != 0 && h->view.loss != DAB_LOSS_TRIVIAL)
+    return set_error(DAB_E_UNSUPPORTED, "pcg_fp32 with a robust loss is not supported (set pcg_fp32 = 0 or DAB_LOSS_TRIVIAL)");
   if (opt.linear_solver_type != DAB_LINEAR_SOLVER_EXPLICIT_SCHUR &&
       opt.linear_solver_type != DAB_LINEAR_SOLVER_IMPLICIT_SCHUR_PCG &&
       opt.linear_solver_type != DAB_LINEAR_SOLVER_AUTO)

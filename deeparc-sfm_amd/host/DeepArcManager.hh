@@ -47,10 +47,22 @@ class DeepArcManager {
   // filterPoint3d() change the blocks or points.
   DabSession& dabSession();
   unsigned long long structureVersion() const { return structure_version_; }
+  // Robust loss of every solve() of this manager (dab_set_loss: DAB_LOSS_* and Ceres' scale
+  // a). The reference passes NULL and keeps `//new ceres::CauchyLoss(0.5)` beside it
+  // (sfm.cc:48-49); the default here is that NULL (DAB_LOSS_TRIVIAL). Checked when the solve
+  // applies it to the handle. filterPoint3d keeps using the bare residual, as the reference's.
+  void setLoss(int loss_type, double scale) {
+    loss_type_ = loss_type;
+    loss_scale_ = scale;
+  }
+  int lossType() const { return loss_type_; }
+  double lossScale() const { return loss_scale_; }
 
  private:
   std::unique_ptr<DabSession> session_;
   unsigned long long structure_version_ = 0;
+  int loss_type_ = 0;  // DAB_LOSS_TRIVIAL
+  double loss_scale_ = 1.0;
   int arc_size_ = 0, ring_size_ = 0;
   bool share_extrinsic_ = false;
   std::map<int, std::map<int, Camera*> > hemisphere_;

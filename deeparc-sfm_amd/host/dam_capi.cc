@@ -130,6 +130,18 @@ int dam_solve(dam_manager* m, int32_t max_iteration, int32_t max_second, int32_t
   });
 }
 
+int dam_set_loss(dam_manager* m, int32_t loss_type, double scale) {
+  return guarded([&] {
+    if (!m) throw "null manager";
+    const bool known = loss_type == DAB_LOSS_TRIVIAL || loss_type == DAB_LOSS_HUBER ||
+                       loss_type == DAB_LOSS_SOFT_L1 || loss_type == DAB_LOSS_CAUCHY;
+    if (!known) throw "unknown loss type";
+    if (loss_type != DAB_LOSS_TRIVIAL && !(scale > 0.0 && scale <= 1.7976931348623157e308))
+      throw "loss scale must be finite and > 0";
+    m->m.setLoss(loss_type, scale);
+  });
+}
+
 int dam_filter(dam_manager* m, double error_boundary, const double center[3], double radius) {
   return guarded([&] {
     double c[3] = {center[0], center[1], center[2]};

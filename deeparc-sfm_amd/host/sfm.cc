@@ -20,6 +20,8 @@ int solveWith(DeepArcManager& m, const dab_options& options, bool freeze_camera,
   DabScene& scene = S.scene;
   dab_summary local{};
   dab_summary* s = summary ? summary : &local;
+  rc = dab_set_loss(dh.h, m.lossType(), m.lossScale());  // sfm.cc:48: the residual blocks' loss
+  if (rc) return rc;
   const double t0 = dab_now_seconds();
   rc = dab_solve(dh.h, &options, s);
   if (rc == DAB_E_UNSUPPORTED && options.linear_solver_type == DAB_LINEAR_SOLVER_EXPLICIT_SCHUR) {
@@ -227,9 +229,11 @@ void fitHemisphere(const std::vector<std::vector<double> >& centers, double cent
 }
 
 PipelineReport runPipeline(const std::string& input, const std::string& output, const std::string& ply_prefix,
-                           int max_iteration, int max_second, double error_boundary, bool verbose) {
+                           int max_iteration, int max_second, double error_boundary, bool verbose, int loss_type,
+                           double loss_scale) {
   const double t_start = now_seconds();
   DeepArcManager m;
+  m.setLoss(loss_type, loss_scale);
   m.read(input);
   PipelineReport rep{};
   const double t_read = now_seconds();

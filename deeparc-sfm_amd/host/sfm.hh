@@ -18,6 +18,8 @@
 void solve(DeepArcManager& deeparcManager, int max_iteration = 1000, int max_second = 3600,
            bool freeze_camera = false);
 // Same, with explicit options; fills *summary when non-null. Returns 0 or a DAB_E_* code.
+// Every solve applies the manager's robust loss (DeepArcManager::setLoss; the reference's
+// NULL loss of sfm.cc:48 by default) to the handle first.
 int solveWith(DeepArcManager& m, const dab_options& options, bool freeze_camera, dab_summary* summary);
 
 // Least-squares fit of centre c and squared radius R to the camera centres, from
@@ -43,4 +45,4 @@ struct PipelineReport {
 // per-iteration progress and the per-solve summary line the reference prints.
 PipelineReport runPipeline(const std::string& input, const std::string& output, const std::string& ply_prefix,
                            int max_iteration = 100, int max_second = 3600, double error_boundary = 5.0,
-                           bool verbose = true);
+                           bool verbose = true, int loss_type = DAB_LOSS_TRIVIAL, double loss_scale = 1.0);

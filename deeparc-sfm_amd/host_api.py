@@ -44,6 +44,7 @@ SIGNATURES = {
     "dam_get_blocks": (C.c_int, [C.c_void_p, _ip, _ip, _ip, _dp]),
     "dam_solve": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                             C.POINTER(_abi.DabSummary)]),
+    "dam_set_loss": (C.c_int, [C.c_void_p, C.c_int32, C.c_double]),
     "dam_filter": (C.c_int, [C.c_void_p, C.c_double, _dp, C.c_double]),
     "dam_camera_centers": (C.c_int, [C.c_void_p, _dp, C.c_int32, _ip]),
     "dam_fit_hemisphere": (C.c_int, [_dp, C.c_int32, _dp, _dp, C.c_int32]),
@@ -137,6 +138,11 @@ class DeepArcManager:
         out = np.zeros((n.value, 3))
         _check(self.lib.dam_camera_centers(self.h, _p(out, C.c_double), n.value, C.byref(n)))
         return out
+
+    def set_loss(self, kind, scale=1.0):
+        """Robust loss of every later solve() of this manager (dam_set_loss): kind as
+        core.Solver.set_loss, e.g. set_loss("cauchy", 0.5) for `new ceres::CauchyLoss(0.5)`."""
+        _check(self.lib.dam_set_loss(self.h, _abi.loss_kind(kind), float(scale)))
 
     def filterPoint3d(self, error_boundary, hemisphere_center, hemisphere_radius):  # noqa: N802
         c = np.ascontiguousarray(hemisphere_center, np.float64)

@@ -230,6 +230,37 @@ int dab_set_problem(dab_handle* h, const dab_problem* p);
 /* Re-upload only the parameter values (points, ext) of the current problem. */
 int dab_update_parameters(dab_handle* h, const double* points, const double* ext);
 int dab_solve(dab_handle* h, const dab_options* opt, dab_summary* summary);
+
+/* ---- robust loss ------------------------------------------------------------------------
+ * The reference adds every residual block with a NULL loss and keeps
+ * `//new ceres::CauchyLoss(0.5)` commented out beside it (sfm.cc:48-49); its outer
+ * solve -> filterPoint3d -> solve loop stands in for one. Here the loss is state of the
+ * handle, one for every observation. Ceres' definitions (an assumption labelled like SURVEY
+ * App. B), with s = ru^2 + rv^2 per observation, a = scale, b = a^2, c = 1 / b:
+ *   TRIVIAL     rho = s                               rho' = 1
+ *   HUBER(a)    s <= b: s, else 2 a sqrt(s) - b       s <= b: 1, else max(DBL_MIN, a / sqrt(s))
+ *   SOFT_L1(a)  2 b (sqrt(1 + s c) - 1)               max(DBL_MIN, 1 / sqrt(1 + s c))
+ *   CAUCHY(a)   b log(1 + s c)                        max(DBL_MIN, 1 / (1 + s c))
+ * All have rho'' <= 0, so Ceres' Corrector scales residual and Jacobian rows by sqrt(rho'(s))
+ * at the linearisation point (alpha = 0): gradient, blocks, Jacobi scaling, Schur complement,
+ * PCG, back substitution and the model cost change all use the scaled rows. Every cost
+ * dab_solve reports (initial, per iteration, final) is 0.5 sum rho(s), not 0.5 |scaled r|^2.
+ * dab_eval_residuals, dab_eval_jacobians and dab_filter keep returning the raw residuals,
+ * Jacobians and 0.5 sum r^2 (the reference's filter calls the bare functor).
+ *
+ * The loss defaults to TRIVIAL, survives dab_set_problem and dab_update_parameters, and takes
+ * effect at the next dab_solve, dab_bench_eval_pass or dab_bench_get_blocks (under a loss the
+ * blocks are those of the scaled rows and *cost = 0.5 sum rho). In a multi-rank handle every
+ * rank must set the same loss. DAB_E_INVALID (loss unchanged) for a null handle (checked
+ * before any device use), an unknown type, or a scale that is not finite and > 0; the scale
+ * is ignored for TRIVIAL. dab_solve with pcg_fp32 != 0 and a non-trivial loss returns
+ * DAB_E_UNSUPPORTED: the fp32 matrix-free product never forms a residual to weight. */
+#define DAB_LOSS_TRIVIAL 0
+#define DAB_LOSS_HUBER   1
+#define DAB_LOSS_SOFT_L1 2
+#define DAB_LOSS_CAUCHY  3
+int dab_set_loss(dab_handle* h, int32_t loss_type, double scale);
+int dab_get_loss(dab_handle* h, int32_t* loss_type, double* scale);
 /* Copy the device-resident parameters into host arrays (either may be NULL). */
 int dab_get_parameters(dab_handle* h, double* points, double* ext);
 

@@ -48,6 +48,10 @@ int dam_get_blocks(dam_manager* m, int32_t* pos_arc, int32_t* pos_ring, int32_t*
  * summary may be NULL */
 int dam_solve(dam_manager* m, int32_t max_iteration, int32_t max_second, int32_t freeze_camera,
               int32_t linear_solver_type, dab_summary* summary);
+/* Robust loss (DAB_LOSS_*, scale; dab_set_loss in dab.h) of every later solve of this
+ * manager; the default is the reference's NULL loss (sfm.cc:48-49). A bad type or scale
+ * returns an error and leaves the loss as it was. dam_filter keeps the bare residual. */
+int dam_set_loss(dam_manager* m, int32_t loss_type, double scale);
 int dam_filter(dam_manager* m, double error_boundary, const double center[3], double radius);
 /* out [capacity][3]; *count = number of centres (may exceed capacity) */
 int dam_camera_centers(dam_manager* m, double* out, int32_t capacity, int32_t* count);

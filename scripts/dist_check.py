@@ -6,7 +6,8 @@ Every rank solves its point shard of one global problem through dab_create_dist;
 also solves the global problem on one handle and compares the LM trajectories (explicit
 Schur and PCG). With --device D every rank uses device D (ranks sharing one GPU; RCCL
 refuses that, so pair it with --host-collective, which stages the library's collectives
-through gloo and exercises every other part of the sharded path).
+through gloo and exercises every other part of the sharded path). --loss kind:scale sets a
+robust loss (dab_set_loss) on every rank's handle and on the single handle it is compared with.
 """
 import argparse
 import json
@@ -46,7 +47,13 @@ def main():
     ap.add_argument("--timeout-rank", type=int, default=-1,
                     help="this rank's evaluation pass runs a frame wait that never completes "
                     "(DAB_EVAL_SIDE=7): every rank's dab_solve must fail with the timeout, none may hang")
+    ap.add_argument("--loss", default="", help="robust loss kind:scale (huber | soft_l1 | cauchy, e.g. "
+                    "cauchy:0.5), set on every rank's handle and on the single-handle comparison")
     a = ap.parse_args()
+    loss = None
+    if a.loss:
+        kind, _, scale = a.loss.partition(":")
+        loss = (kind, float(scale) if scale else 1.0)
     rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
     dev = a.device if a.device >= 0 else int(os.environ.get("LOCAL_RANK", "0"))
     import torch
@@ -108,6 +115,8 @@ def main():
         if a.live_together:  # every handle of this problem created (and its arena slot taken) up front
             for _ in range(3):
                 h = pkg.Solver(dev, rank, world, uid, host_allreduce=gloo_allreduce if a.host_collective else None)
+                if loss:
+                    h.set_loss(*loss)
                 live.append(h)
         for li, lst in enumerate(solvers):
             opts = pkg.options(max_num_iterations=a.iters, linear_solver_type=lst)
@@ -115,6 +124,8 @@ def main():
             if rank == 0:
                 g1 = glob.copy()
                 s1 = pkg.Solver(dev)
+                if loss:
+                    s1.set_loss(*loss)
                 s1.set_problem(g1)
                 ropts = opts
                 if lst == pkg.DAB_LINEAR_SOLVER_AUTO:
@@ -129,6 +140,8 @@ def main():
             mine = glob.copy().shard(rank, world)
             s = live[li] if live else pkg.Solver(dev, rank, world, uid,
                                                  host_allreduce=gloo_allreduce if a.host_collective else None)
+            if loss and not live:
+                s.set_loss(*loss)  # the same loss on every rank (include/dab.h)
             s.set_problem(mine)
             sched = s.eval_fused()
             p2p = s.comm_p2p()
