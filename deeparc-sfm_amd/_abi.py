@@ -97,6 +97,25 @@ class DabSummary(C.Structure):
     ]
 
 
+class DabCovarianceOptions(C.Structure):
+    _fields_ = [("min_pivot_ratio", C.c_double), ("jacobi_scaling", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class DabCovarianceInfo(C.Structure):
+    _fields_ = [
+        ("status", C.c_int32), ("num_free_ext", C.c_int32), ("num_free_points", C.c_int32),
+        ("first_deficient_point", C.c_int32), ("deficient_points", C.c_int32),
+        ("schur_assembly", C.c_int32), ("point_pivot_ratio_min", C.c_double),
+        ("camera_pivot_ratio", C.c_double), ("cost", C.c_double), ("num_residuals", C.c_int32),
+        ("num_parameters", C.c_int32), ("evaluate_ms", C.c_double), ("factor_ms", C.c_double),
+        ("inverse_ms", C.c_double), ("points_ms", C.c_double),
+    ]
+
+
+COV_STATUS = {0: "OK", 1: "RANK_DEFICIENT"}
+
+
 class DabSynthConfig(C.Structure):
     _fields_ = [
         ("kind", C.c_int32), ("num_cameras", C.c_int32), ("num_arcs", C.c_int32),
@@ -129,6 +148,9 @@ SIGNATURES = {
     "dab_set_loss": (C.c_int, [C.c_void_p, C.c_int32, C.c_double]),
     "dab_get_loss": (C.c_int, [C.c_void_p, _ip, _dp]),
     "dab_get_parameters": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "dab_covariance_options_init": (None, [C.POINTER(DabCovarianceOptions)]),
+    "dab_covariance": (C.c_int, [C.c_void_p, C.POINTER(DabCovarianceOptions), _dp, _dp, _dp,
+                                 C.POINTER(DabCovarianceInfo)]),
     "dab_eval_residuals": (C.c_int, [C.c_void_p, _dp, _dp]),
     "dab_eval_jacobians": (C.c_int, [C.c_void_p, _dp, _dp]),
     "dab_filter": (C.c_int, [C.c_void_p, C.c_double, _dp, C.c_double, _u8p, _u8p, _ip, _ip]),

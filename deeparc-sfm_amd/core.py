@@ -15,8 +15,8 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import (DabOptions, DabProblem, DabSummary, DabIteration, DabSynthConfig, check,
-                   load_library)
+from ._abi import (DabOptions, DabProblem, DabSummary, DabIteration, DabSynthConfig,
+                   DabCovarianceOptions, DabCovarianceInfo, check, load_library)
 
 
 def _ptr(a, ct):
@@ -150,6 +150,28 @@ def options(**kw):
     return o
 
 
+def covariance_options(**kw):
+    """dab_covariance_options with the library's defaults (min_pivot_ratio 1e-10,
+    jacobi_scaling 1), then the given fields."""
+    lib = load_library()
+    o = DabCovarianceOptions()
+    lib.dab_covariance_options_init(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(f"unknown option {k}")
+        setattr(o, k, v)
+    return o
+
+
+def _unpack_sym(a, n):
+    """[m][n (n + 1) / 2] upper-packed rows -> [m][n][n] symmetric."""
+    iu = np.triu_indices(n)
+    out = np.zeros((a.shape[0], n, n))
+    out[:, iu[0], iu[1]] = a
+    out[:, iu[1], iu[0]] = a
+    return out
+
+
 def summary_to_dict(s, its):
     return dict(
         initial_cost=s.initial_cost, final_cost=s.final_cost, num_iterations=s.num_iterations,
@@ -255,6 +277,41 @@ class Solver:
         s.iterations_capacity = max_records
         check(self.lib.dab_solve(self.h, C.byref(o), C.byref(s)), self.lib)
         return summary_to_dict(s, its)
+
+    def covariance(self, points=True, ext=True, full=False, **opts):
+        """Sigma = (J^T J)^-1 at the parameters on the handle (dab_covariance; no sigma^2 factor:
+        multiply by 2 info["cost"] / (num_residuals - num_parameters)). Returns a dict with
+        `info`, `point_cov` (num_points, 3, 3) with NaN rows for unreferenced points, `ext_cov`
+        (nfe, 6, 6) with `ext_index` (the extrinsic of each block; None on a shard whose free set
+        is a union over ranks), and `ext_full` (6 nfe, 6 nfe) when full. When info["status"] is
+        "RANK_DEFICIENT" the arrays are None: drop single-observation points (Problem.subset) or
+        fix the scale gauge with one more constant extrinsic. Two library calls: the size and
+        rank query, then the arrays."""
+        o = covariance_options(**opts)
+        info = DabCovarianceInfo()
+        check(self.lib.dab_covariance(self.h, C.byref(o), None, None, None, C.byref(info)), self.lib)
+        nfe, npts = info.num_free_ext, int(self.problem.points.shape[0])
+        pc = np.zeros((npts, 6)) if points else None
+        ec = np.zeros((nfe, 21)) if ext else None
+        ef = np.zeros((6 * nfe, 6 * nfe)) if full else None
+        if info.status == 0 and (points or ext or full):
+            check(self.lib.dab_covariance(self.h, C.byref(o), _ptr(pc, C.c_double), _ptr(ec, C.c_double),
+                                          _ptr(ef, C.c_double), C.byref(info)), self.lib)
+        d = {k: getattr(info, k) for k, _ in DabCovarianceInfo._fields_}
+        d["status"] = _abi.COV_STATUS.get(info.status, str(info.status))
+        ok = info.status == 0
+        pr = self.problem
+        idx = None
+        if not pr.freeze_camera:
+            used = np.unique(np.concatenate([pr.obs_ext0, pr.obs_ext1[pr.obs_ext1 >= 0]]))
+            if pr.ext_const is not None:
+                used = used[pr.ext_const[used] == 0]
+            idx = used.astype(np.int32) if used.shape[0] == nfe else None
+        elif nfe == 0:
+            idx = np.zeros(0, np.int32)
+        return dict(info=d, point_cov=_unpack_sym(pc, 3) if ok and points else None,
+                    ext_cov=_unpack_sym(ec, 6) if ok and ext else None, ext_index=idx,
+                    ext_full=ef if ok and full else None)
 
     def residuals(self):
         r = np.zeros((self.problem.num_obs, 2))

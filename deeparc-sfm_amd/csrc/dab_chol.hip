@@ -1374,6 +1374,8 @@ int chol_guard_check(CholCtx* c, const char* where, std::string* first) {
   return c ? c->mem.guard_check(where, first) : 0;
 }
 Dev* chol_mem(CholCtx* c) { return c ? &c->mem : nullptr; }
+static_assert(kCholBlk == kBlk && kCholBlkL == 1024 && NB == 64, "dab_cov.hip reads the block scratch by these");
+const double* chol_diag_blocks(CholCtx* c) { return c ? c->blk : nullptr; }
 
 // Loads this translation unit's code object on the current device now: otherwise the first
 // launch of any of its kernels pays for it (10-40 ms, inside a process's first LM iteration).

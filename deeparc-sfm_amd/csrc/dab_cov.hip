@@ -1,0 +1,405 @@
+// dab_cov.hip — covariance at the solution (dab_covariance): the inverse of the reduced camera
+// system from its Cholesky factor, and the per-point fold-back of the camera covariance.
+//
+// With L the row-major lower factor of the Jacobi-scaled, undamped S (dab_chol.hip: the blocks
+// left of the diagonal in S's buffer, the factored diagonal blocks in the factorisation's
+// scratch, chol_diag_blocks), the scaled camera covariance is C = S^-1 = L^-T L^-1 = Z^T Z with
+// Z = L^-1:
+//   k_cov_diag_inv   Z_ii = L_ii^-1 for every 64x64 diagonal block (one launch; the blocks
+//                    are independent; scalar forward substitution, 64 columns side by side)
+//   k_cov_trsm_row   block row i of Z below the diagonal: Z_ij = -Z_ii sum_{k=j}^{i-1} L_ik Z_kj
+//                    (fp64 MFMA; one launch per block row, rows 1..nb-1 in stream order)
+//   k_cov_ztz        the lower triangle of Z^T Z by 64x64 tiles, mirrored (fp64 MFMA; one
+//                    launch). C may overwrite L: only Z is read.
+// Nothing here waits on another work-group: every dependency is a launch boundary. Every sum
+// runs in one fixed order, so two calls give bitwise the same arrays. Indices >= n (n < 64, a
+// partial last block) read as zero and are never written.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+
+#include "dab_kernels.h"
+
+namespace dab {
+
+namespace {
+constexpr int CB = 64;    // block size of the blocked inverse
+constexpr int CLS = 65;   // LDS row stride of the diagonal-block kernel
+typedef double dbl4 __attribute__((ext_vector_type(4)));
+
+// min / max / non-finite count of the factor's squared diagonal -> out[3] (one work-group)
+__global__ __launch_bounds__(256) void k_cov_diag_minmax(int n, const double* __restrict__ Ld,
+                                                         double* __restrict__ out) {
+  __shared__ double smin[256], smax[256], sbad[256];
+  double mn = INFINITY, mx = 0.0, bad = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const double d = Ld[(size_t)kCholBlk * (i / CB) + kCholBlkL + (i % CB) * (CB + 1)];
+    const double d2 = d * d;
+    if (!isfinite(d2) || !(d > 0.0)) {
+      bad += 1.0;
+    } else {
+      mn = fmin(mn, d2);
+      mx = fmax(mx, d2);
+    }
+  }
+  smin[threadIdx.x] = mn;
+  smax[threadIdx.x] = mx;
+  sbad[threadIdx.x] = bad;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) {
+      smin[threadIdx.x] = fmin(smin[threadIdx.x], smin[threadIdx.x + w]);
+      smax[threadIdx.x] = fmax(smax[threadIdx.x], smax[threadIdx.x + w]);
+      sbad[threadIdx.x] += sbad[threadIdx.x + w];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    out[0] = smin[0];
+    out[1] = smax[0];
+    out[2] = sbad[0];
+  }
+}
+
+// Z_ii = L_ii^-1. Thread c owns column c of the block: z_r = (delta_rc - sum_{c<=k<r} L_rk z_k)
+// / L_rr. The strictly lower part of the LDS tile holds L, its upper part (diagonal included)
+// the columns of Z transposed (thread c writes row c only), the reciprocal diagonal apart.
+__global__ __launch_bounds__(CB) void k_cov_diag_inv(int n, const double* __restrict__ Ld,
+                                                     double* __restrict__ Z, int ldz) {
+  __shared__ double T[CB][CLS];
+  __shared__ double dinv[CB];
+  const int b0 = blockIdx.x * CB, c = threadIdx.x;
+  const int nr = min(CB, n - b0);
+  const double* L = Ld + (size_t)kCholBlk * blockIdx.x + kCholBlkL;  // L_bb [64][64]
+  for (int r = 0; r < nr; ++r) {
+    if (c < nr) T[r][c] = c < r ? L[r * CB + c] : 0.0;
+  }
+  if (c < nr) dinv[c] = 1.0 / L[c * CB + c];
+  __syncthreads();
+  if (c < nr) {
+    T[c][c] = dinv[c];
+    for (int r = c + 1; r < nr; ++r) {
+      double acc = 0.0;
+      for (int k = c; k < r; ++k) acc = fma(T[r][k], T[c][k], acc);  // L[r][k] * z_k
+      T[c][r] = -acc * dinv[r];
+    }
+  }
+  __syncthreads();
+  // the whole tile goes out (zeros above the diagonal): the later passes read full tiles
+  for (int r = 0; r < nr; ++r)
+    if (c < nr) Z[(size_t)(b0 + r) * ldz + b0 + c] = c <= r ? T[c][r] : 0.0;
+}
+
+// Block row i of Z left of the diagonal. Work-group (j, strip): the 64 x 16 strip of Z_ij,
+// wave w its rows 16 w .. 16 w + 15.
+__global__ __launch_bounds__(256) void k_cov_trsm_row(int i, int n, const double* __restrict__ L, int lda,
+                                                      double* __restrict__ Z, int ldz) {
+  __shared__ double Ts[CB][17];
+  const int j = blockIdx.x >> 2, strip = blockIdx.x & 3;
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
+  const int i0 = i * CB, c0 = j * CB + 16 * strip;
+  const int arow = i0 + 16 * w + li;
+  const bool arow_ok = arow < n;
+  // T = sum_k L_ik Z_kj over the block columns j .. i-1 (all indices < i0 <= n there)
+  dbl4 acc = {0.0, 0.0, 0.0, 0.0};
+  const double* Lr = L + (size_t)(arow_ok ? arow : 0) * lda;
+  for (int k0 = j * CB; k0 < i0; k0 += 16) {
+    double a[4], b[4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      const int k = k0 + 4 * ks + lk;
+      a[ks] = arow_ok ? Lr[k] : 0.0;
+      b[ks] = Z[(size_t)k * ldz + c0 + li];
+    }
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks], b[ks], acc, 0, 0, 0);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) Ts[16 * w + lk + 4 * r][li] = acc[r];
+  __syncthreads();
+  // Z_ij = -Z_ii T
+  dbl4 out = {0.0, 0.0, 0.0, 0.0};
+  const double* Zr = Z + (size_t)(arow_ok ? arow : 0) * ldz;
+#pragma unroll
+  for (int ks = 0; ks < CB / 4; ++ks) {
+    const int k = 4 * ks + lk;
+    const double a = (arow_ok && i0 + k < n) ? -Zr[i0 + k] : 0.0;
+    out = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Ts[k][li], out, 0, 0, 0);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = i0 + 16 * w + lk + 4 * r;
+    if (row < n) Z[(size_t)row * ldz + c0 + li] = out[r];
+  }
+}
+
+// C tile (i, j <= i) = sum_{k >= 64 i} Z[k][i-block]^T Z[k][j-block]; wave w: rows 16 w.. of the
+// tile, all four 16-column tiles. The tile and its mirror are written (a diagonal tile from
+// its lower half), so C is symmetric bitwise.
+__global__ __launch_bounds__(256) void k_cov_ztz(int n, const double* __restrict__ Z, int ldz,
+                                                 double* __restrict__ C, int ldc) {
+  const int i = blockIdx.y, j = blockIdx.x;
+  if (j > i) return;
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
+  const int i0 = i * CB, j0 = j * CB;
+  const int acol = i0 + 16 * w + li;
+  const bool acol_ok = acol < n;
+  bool bcol_ok[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) bcol_ok[t] = j0 + 16 * t + li < n;
+  dbl4 acc[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) acc[t] = dbl4{0.0, 0.0, 0.0, 0.0};
+  for (int k0 = i0; k0 < n; k0 += 4) {
+    const int k = k0 + lk;
+    const bool kok = k < n;
+    const double* Zk = Z + (size_t)(kok ? k : 0) * ldz;
+    const double a = (kok && acol_ok) ? Zk[acol] : 0.0;
+    double b[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) b[t] = (kok && bcol_ok[t]) ? Zk[j0 + 16 * t + li] : 0.0;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[t], acc[t], 0, 0, 0);
+  }
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = i0 + 16 * w + lk + 4 * r, col = j0 + 16 * t + li;
+      if (row >= n || col >= n || col > row) continue;
+      C[(size_t)row * ldc + col] = acc[t][r];
+      C[(size_t)col * ldc + row] = acc[t][r];
+    }
+}
+
+// per point: pivot ratio of the scaled undamped V (the same arithmetic as k_point_factor with a
+// zero LM diagonal) -> ratio[NP]; partial[grid] = deficient counts, partial[grid + b] = min ratio
+__global__ __launch_bounds__(256) void k_cov_point_rank(int NP, const double* __restrict__ V,
+                                                        const double* __restrict__ sp, double thr,
+                                                        double* __restrict__ ratio, double* __restrict__ partial) {
+  __shared__ double scnt[256], sneg[256];
+  double cnt = 0.0, neg = INFINITY;  // neg: the smallest ratio
+  const size_t NPs = (size_t)NP;
+  for (int p = blockIdx.x * 256 + threadIdx.x; p < NP; p += gridDim.x * 256) {
+    const double s0 = sp[p], s1 = sp[NPs + p], s2 = sp[2 * NPs + p];
+    const double v00 = s0 * V[p] * s0, v01 = s0 * V[NPs + p] * s1, v02 = s0 * V[2 * NPs + p] * s2;
+    const double v11 = s1 * V[3 * NPs + p] * s1, v12 = s1 * V[4 * NPs + p] * s2, v22 = s2 * V[5 * NPs + p] * s2;
+    const double l00 = sqrt(v00);
+    const double l10 = v01 / l00, l20 = v02 / l00;
+    const double d1 = v11 - l10 * l10;
+    const double l21 = (v12 - l20 * l10) / sqrt(d1);
+    const double d2 = v22 - l20 * l20 - l21 * l21;
+    const double mx = fmax(v00, fmax(d1, d2)), mn = fmin(v00, fmin(d1, d2));
+    double q = mn / mx;
+    // fmin / fmax skip a NaN pivot (one that follows a negative one, which is then the minimum)
+    if (!(v00 > 0.0) || isnan(q)) q = -INFINITY;
+    ratio[p] = q;
+    if (!(q > thr)) cnt += 1.0;
+    neg = fmin(neg, q);
+  }
+  scnt[threadIdx.x] = cnt;
+  sneg[threadIdx.x] = neg;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) {
+      scnt[threadIdx.x] += scnt[threadIdx.x + w];
+      sneg[threadIdx.x] = fmin(sneg[threadIdx.x], sneg[threadIdx.x + w]);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x] = scnt[0];
+    partial[gridDim.x + blockIdx.x] = sneg[0];
+  }
+}
+
+// One record per distinct free camera of a point ("the record" of the tile path): the sum of the
+// Y of the point's entries with that camera, in entry order, at slot pt_ent_ptr[p] + i of
+// Ym [NE][18] / mcam [NE]; mcnt[p] = the number of distinct cameras. Thread = point.
+__global__ __launch_bounds__(256) void k_cov_merge(DevView v, const double* __restrict__ Y, double* __restrict__ Ym,
+                                                   int* __restrict__ mcam, int* __restrict__ mcnt) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= v.NP) return;
+  const int eb = v.pt_ent_ptr[p], ee = v.pt_ent_ptr[p + 1];
+  int n = 0;
+  for (int e = eb; e < ee; ++e) {
+    const int ce = v.ent_cam[e];
+    bool lead = true;  // the first entry of its camera
+    for (int g = eb; g < e; ++g) lead = lead && v.ent_cam[g] != ce;
+    if (!lead) continue;
+    double y[18];
+    const double2* ys = reinterpret_cast<const double2*>(Y + (size_t)kYRec * v.ent_pos[e]);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+      const double2 t = ys[k];
+      y[2 * k] = t.x;
+      y[2 * k + 1] = t.y;
+    }
+    for (int g = e + 1; g < ee; ++g) {
+      if (v.ent_cam[g] != ce) continue;
+      const double2* gs = reinterpret_cast<const double2*>(Y + (size_t)kYRec * v.ent_pos[g]);
+#pragma unroll
+      for (int k = 0; k < 9; ++k) {
+        const double2 t = gs[k];
+        y[2 * k] += t.x;
+        y[2 * k + 1] += t.y;
+      }
+    }
+    double2* dst = reinterpret_cast<double2*>(Ym + (size_t)kYRec * (eb + n));
+#pragma unroll
+    for (int k = 0; k < 9; ++k) dst[k] = make_double2(y[2 * k], y[2 * k + 1]);
+    mcam[eb + n] = ce;
+    ++n;
+  }
+  mcnt[p] = n;
+}
+
+// Sigma_pp = PU (I + sum_{e,e'} Y_e^T C_{c(e) c(e')} Y_e') PU^T, thread = point. With Z_c the sum
+// of the Y of the point's entries of camera c (k_cov_merge) the sum over all ordered pairs of
+// entries is the sum over ordered pairs of distinct cameras of Z_c^T C_cd Z_d, folded by C's
+// symmetry: the pair (c, d before c) contributes G + G^T, the pair (c, c) G, so a point of k
+// distinct cameras gathers k (k + 1) / 2 blocks, in record order (fixed). C: the scaled camera
+// covariance, both triangles.
+__global__ __launch_bounds__(256) void k_cov_points(DevView v, int with_cams, const double* __restrict__ PU,
+                                                    const double* __restrict__ Ym, const int* __restrict__ mcam,
+                                                    const int* __restrict__ mcnt, const double* __restrict__ C,
+                                                    int ldc, double* __restrict__ out) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= v.NP) return;
+  double m00 = 1.0, m01 = 0.0, m02 = 0.0, m11 = 1.0, m12 = 0.0, m22 = 1.0;
+  if (with_cams) {
+    const int eb = v.pt_ent_ptr[p], ee = eb + mcnt[p];
+    for (int e = eb; e < ee; ++e) {
+      double ye[18];
+      const double2* ys = reinterpret_cast<const double2*>(Ym + (size_t)kYRec * e);
+#pragma unroll
+      for (int k = 0; k < 9; ++k) {
+        const double2 t = ys[k];
+        ye[2 * k] = t.x;
+        ye[2 * k + 1] = t.y;
+      }
+      const double* Crow = C + (size_t)6 * mcam[e] * ldc;
+      for (int f = eb; f <= e; ++f) {
+        double yf[18];
+        const double2* fs = reinterpret_cast<const double2*>(Ym + (size_t)kYRec * f);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+          const double2 t = fs[k];
+          yf[2 * k] = t.x;
+          yf[2 * k + 1] = t.y;
+        }
+        const double* Cb = Crow + (size_t)6 * mcam[f];
+        double g[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+#pragma unroll
+        for (int a = 0; a < 6; ++a) {
+          double t0 = 0.0, t1 = 0.0, t2 = 0.0;  // row a of C_ef Y_f
+#pragma unroll
+          for (int b = 0; b < 6; ++b) {
+            const double cab = Cb[(size_t)a * ldc + b];
+            t0 = fma(cab, yf[3 * b], t0);
+            t1 = fma(cab, yf[3 * b + 1], t1);
+            t2 = fma(cab, yf[3 * b + 2], t2);
+          }
+#pragma unroll
+          for (int i = 0; i < 3; ++i) {
+            g[i][0] = fma(ye[3 * a + i], t0, g[i][0]);
+            g[i][1] = fma(ye[3 * a + i], t1, g[i][1]);
+            g[i][2] = fma(ye[3 * a + i], t2, g[i][2]);
+          }
+        }
+        if (f == e) {  // symmetric up to rounding: its symmetric part
+          m00 += g[0][0];
+          m11 += g[1][1];
+          m22 += g[2][2];
+          m01 += 0.5 * (g[0][1] + g[1][0]);
+          m02 += 0.5 * (g[0][2] + g[2][0]);
+          m12 += 0.5 * (g[1][2] + g[2][1]);
+        } else {
+          m00 += 2.0 * g[0][0];
+          m11 += 2.0 * g[1][1];
+          m22 += 2.0 * g[2][2];
+          m01 += g[0][1] + g[1][0];
+          m02 += g[0][2] + g[2][0];
+          m12 += g[1][2] + g[2][1];
+        }
+      }
+    }
+  }
+  const double* pu = PU + 6 * (size_t)p;
+  const double u00 = pu[0], u01 = pu[1], u02 = pu[2], u11 = pu[3], u12 = pu[4], u22 = pu[5];
+  // W = PU M (PU upper triangular), Sigma = W PU^T
+  const double w00 = u00 * m00 + u01 * m01 + u02 * m02, w01 = u00 * m01 + u01 * m11 + u02 * m12,
+               w02 = u00 * m02 + u01 * m12 + u02 * m22;
+  const double w11 = u11 * m11 + u12 * m12, w12 = u11 * m12 + u12 * m22;
+  const double w10 = u11 * m01 + u12 * m02;
+  const double w22 = u22 * m22, w21 = u22 * m12, w20 = u22 * m02;
+  (void)w10; (void)w20; (void)w21;
+  double* o = out + 6 * (size_t)p;
+  o[0] = w00 * u00 + w01 * u01 + w02 * u02;
+  o[1] = w01 * u11 + w02 * u12;
+  o[2] = w02 * u22;
+  o[3] = w11 * u11 + w12 * u12;
+  o[4] = w12 * u22;
+  o[5] = w22 * u22;
+}
+
+// Sigma_cc' = s_c C s_c' in place (the product of the two scales first: symmetric bitwise)
+__global__ __launch_bounds__(256) void k_cov_unscale(int n, const double* __restrict__ sc, double* __restrict__ C,
+                                                     int ldc) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (size_t)n * n) return;
+  const size_t i = t / n, j = t - i * n;
+  C[i * ldc + j] *= sc[i] * sc[j];
+}
+// the 6x6 diagonal blocks, upper-packed -> out[NC][21]
+__global__ __launch_bounds__(256) void k_cov_ext_blocks(int NC, const double* __restrict__ C, int ldc,
+                                                        double* __restrict__ out) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= 21 * NC) return;
+  const int c = t / 21, q = t - 21 * c;
+  int a = 0, rem = q;
+  while (rem >= 6 - a) {
+    rem -= 6 - a;
+    ++a;
+  }
+  const int b = a + rem;
+  out[t] = C[(size_t)(6 * c + a) * ldc + 6 * c + b];
+}
+}  // namespace
+
+void launch_cov_diag_minmax(hipStream_t s, int n, const double* Ld, double* out) {
+  k_cov_diag_minmax<<<1, 256, 0, s>>>(n, Ld, out);
+}
+
+void launch_cov_inverse(hipStream_t s, int n, const double* L, int lda, const double* Ld, double* Z, int ldz,
+                        double* C, int ldc) {
+  if (n <= 0) return;
+  const int nb = (n + CB - 1) / CB;
+  k_cov_diag_inv<<<nb, CB, 0, s>>>(n, Ld, Z, ldz);
+  for (int i = 1; i < nb; ++i) k_cov_trsm_row<<<4 * i, 256, 0, s>>>(i, n, L, lda, Z, ldz);
+  k_cov_ztz<<<dim3(nb, nb), 256, 0, s>>>(n, Z, ldz, C, ldc);
+}
+
+int cov_rank_grid(int NP) { return std::max(1, std::min(256, (NP + 255) / 256)); }
+void launch_cov_point_rank(hipStream_t s, int NP, const double* V, const double* scale_p, double thr, double* ratio,
+                           double* partial, int grid) {
+  k_cov_point_rank<<<grid, 256, 0, s>>>(NP, V, scale_p, thr, ratio, partial);
+}
+
+void launch_cov_points(hipStream_t s, const DevView& v, bool with_cams, const double* PU, const double* Y,
+                       double* Ym, int* mcam, int* mcnt, const double* C, int ldc, double* out) {
+  if (v.NP <= 0) return;
+  const int g = (v.NP + 255) / 256;
+  if (with_cams) k_cov_merge<<<g, 256, 0, s>>>(v, Y, Ym, mcam, mcnt);
+  k_cov_points<<<g, 256, 0, s>>>(v, with_cams ? 1 : 0, PU, Ym, mcam, mcnt, C, ldc, out);
+}
+
+void launch_cov_unscale(hipStream_t s, int NC, const double* scale_c, double* C, int ldc, double* ext_cov) {
+  if (NC <= 0) return;
+  const size_t n = (size_t)6 * NC;
+  k_cov_unscale<<<(unsigned)((n * n + 255) / 256), 256, 0, s>>>((int)n, scale_c, C, ldc);
+  if (ext_cov) k_cov_ext_blocks<<<(21 * NC + 255) / 256, 256, 0, s>>>(NC, C, ldc, ext_cov);
+}
+
+}  // namespace dab

@@ -386,8 +386,36 @@ void chol_destroy(CholCtx*);
 int chol_factor_solve(CholCtx* c, hipStream_t s, int n, double* A, int lda, double* y, int* d_flag);
 int chol_prepare(CholCtx* c, hipStream_t s, int n, double* A, int lda, double* y, int* d_flag);
 int chol_guard_check(CholCtx* c, const char* where, std::string* first);
+// The factorisation keeps the factored 64x64 diagonal blocks in its scratch, not in A (A's
+// diagonal tiles hold the updated, unfactored blocks): block b's L_bb, row-major [64][64] with
+// zeros above the diagonal and an identity tail in a partial last block, is at
+// chol_diag_blocks(c) + kCholBlk * b + kCholBlkL after chol_factor_solve.
+constexpr int kCholBlk = 1024 + 64 * 64, kCholBlkL = 1024;
+const double* chol_diag_blocks(CholCtx* c);
 struct Dev;
 Dev* chol_mem(CholCtx* c);  // the Cholesky scratch's allocator (dab_devmem.h)
+
+// ---- covariance (dab_cov.hip) -------------------------------------------------------------
+// out[3] = {min, max, count of non-positive / non-finite} of the factor's squared diagonal
+// (Ld: the factored diagonal blocks, chol_diag_blocks)
+void launch_cov_diag_minmax(hipStream_t s, int n, const double* Ld, double* out);
+// C = (L L^T)^-1 (both triangles, n x n at ld = ldc) from the row-major lower factor (L: the
+// blocks left of the diagonal ones; Ld: the diagonal blocks, chol_diag_blocks) through
+// Z = L^-1 (n x ldz scratch). C may alias L. Plain stream-ordered launches, fp64 MFMA.
+void launch_cov_inverse(hipStream_t s, int n, const double* L, int lda, const double* Ld, double* Z, int ldz,
+                        double* C, int ldc);
+// pivot ratio (min / max pivot of the 3x3 Cholesky) of every point's scaled undamped V ->
+// ratio[NP]; partial[b] = count of ratios not > thr, partial[grid + b] = min ratio of work-group b
+int cov_rank_grid(int NP);
+void launch_cov_point_rank(hipStream_t s, int NP, const double* V, const double* scale_p, double thr, double* ratio,
+                           double* partial, int grid);
+// Sigma_pp (upper-packed) -> out[NP][6]; Y: [NE][18] records by camera-major position, C: scaled
+// camera covariance; with_cams = false: Sigma_pp = PU PU^T = V^-1. Scratch: Ym [NE][18], mcam
+// [NE], mcnt [NP] (one merged record per distinct camera of a point, k_cov_merge)
+void launch_cov_points(hipStream_t s, const DevView& v, bool with_cams, const double* PU, const double* Y,
+                       double* Ym, int* mcam, int* mcnt, const double* C, int ldc, double* out);
+// C <- s_c C s_c' in place, then its 6x6 diagonal blocks upper-packed -> ext_cov[NC][21] (nullable)
+void launch_cov_unscale(hipStream_t s, int NC, const double* scale_c, double* C, int ldc, double* ext_cov);
 
 int grid_for(int n, int block, int cap);
 

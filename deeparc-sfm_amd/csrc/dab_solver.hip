@@ -21,6 +21,7 @@
 #include <map>
 #include <mutex>
 #include <iterator>
+#include <limits>
 #include <array>
 #include <chrono>
 #include <climits>
@@ -434,6 +435,11 @@ struct dab_handle {
   double *d_V = nullptr, *d_g = nullptr, *d_scale_p = nullptr, *d_scale_c = nullptr;
   double *d_L = nullptr, *d_q = nullptr, *d_Y = nullptr, *d_Yp = nullptr;  // Y camera-/point-major
   double* d_Yrec = nullptr;  // EXPLICIT: Y as [NE][18] records for k_s_blocks (lazy)
+  // dab_covariance (lazy; freed by dab_set_problem): Z = L^-1 [n][lds], the point blocks [NP][6],
+  // the extrinsic blocks [NC][21], the rank test's scalars and partials; events of its stage times
+  double *d_covZ = nullptr, *d_cov_pts = nullptr, *d_cov_ext = nullptr, *d_cov_stat = nullptr;
+  int* d_cov_idx = nullptr;  // [NE] camera of each merged record | [NP] records per point
+  hipEvent_t cov_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   float *d_Y32c = nullptr, *d_Y32p = nullptr;                                 // pcg_fp32 (lazy)
   double* d_camred = nullptr;  // [Ucc NC*21 | gc NC*6 | Ux ncross*36] (all-reduced)
   double* d_partial = nullptr; // chunk partials (max of chunk counts * 36)
@@ -541,6 +547,8 @@ struct dab_handle {
     if (ev1) (void)hipEventDestroy(ev1);
     if (ev2) (void)hipEventDestroy(ev2);
     if (ev3) (void)hipEventDestroy(ev3);
+    for (hipEvent_t e : cov_ev)
+      if (e) (void)hipEventDestroy(e);
     for (auto& e : bench_ev)
       for (hipEvent_t x : e) (void)hipEventDestroy(x);
     if (ev_cam) (void)hipEventDestroy(ev_cam);
@@ -2029,10 +2037,13 @@ static int set_problem_impl(dab_handle* h, const dab_problem* p) {
   CHECK_RC(validate(p));
   HIP_OK(hipSetDevice(h->device));
   HIP_OK(hipStreamSynchronize(h->stream));
+  h->dev.drop(h->d_covZ);  // n x n: back to the device, not into the pool
   h->dev.release();
   // lazily allocated buffers went with the release: clear their pointers so that the next
   // use allocates again (a stale pointer would be written after its memory was freed)
   h->d_Yrec = nullptr;
+  h->d_covZ = h->d_cov_pts = h->d_cov_ext = h->d_cov_stat = nullptr;
+  h->d_cov_idx = nullptr;
   h->d_Y32c = h->d_Y32p = nullptr;
   h->d_Jfull = nullptr;
   h->have_problem = false;
@@ -3425,6 +3436,221 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
   CHECK_RC(dab_get_parameters(h, h->prob.points, h->prob.ext));
   sum->total_time_in_seconds = now_s() - t_start;
   return 0;
+}
+
+// ------------------------------------------------------------------------------------
+// dab_covariance: Sigma = (J^T J)^-1 at the current parameters, by the exact Schur route
+// ------------------------------------------------------------------------------------
+// In the solver's scaled variables (s = the Jacobi scaling dab_solve would use here), with
+// PU_p = s_p L_p^-T, Y_e = (s_c ∘ Jc^T Jp) PU_p and C = (scaled S)^-1:
+//   Sigma_cc' = s_c C_cc' s_c',  Sigma_pp = PU_p (I + sum_{e,e'} Y_e^T C_c(e)c(e') Y_e') PU_p^T.
+// The LM kernels run unchanged with radius = +inf: their sqrt(clamp(d) / radius) is exactly 0.
+static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, double* point_cov, double* ext_cov,
+                           double* ext_full, dab_covariance_info* info) {
+  clear_error();
+  if (!h) return set_error(DAB_E_INVALID, "null handle");
+  dab_covariance_options opt;
+  if (opt_in) opt = *opt_in;
+  else dab_covariance_options_init(&opt);
+  if (!(std::isfinite(opt.min_pivot_ratio) && opt.min_pivot_ratio > 0.0))
+    return set_error(DAB_E_INVALID, "min_pivot_ratio must be finite and > 0");
+  if (!info && !point_cov && !ext_cov && !ext_full) return set_error(DAB_E_INVALID, "null info and null arrays");
+  if (!h->have_problem) return set_error(DAB_E_STATE, "no problem set");
+  HIP_OK(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  const DevView& v = h->view;
+  const int NP = h->NP;
+  if (h->NC > 0) CHECK_RC(build_schur_tables(h));
+  const int NC = h->NC, n = 6 * NC;
+  if (NC > 0 && chol_prepare(h->chol, s, n, h->d_S, h->lds, h->d_yc, h->d_flags + 1) != 0)
+    return set_error(DAB_E_DEVICE, "dense Cholesky set-up failed");
+  dab_covariance_info out{};
+  out.status = DAB_COV_OK;
+  out.num_free_ext = NC;
+  out.num_free_points = NP;
+  out.first_deficient_point = -1;
+  out.schur_assembly = h->schur_tiles ? DAB_SCHUR_TILES : DAB_SCHUR_PAIRS;
+  out.num_residuals = 2 * h->N;
+  out.num_parameters = 3 * NP + 6 * NC;
+  out.point_pivot_ratio_min = out.camera_pivot_ratio = std::numeric_limits<double>::quiet_NaN();
+  for (hipEvent_t& e : h->cov_ev)
+    if (!e) HIP_OK(hipEventCreate(&e));
+  const int rgrid = cov_rank_grid(NP);
+  if (!h->d_cov_stat) CHECK_RC(h->dev.alloc(&h->d_cov_stat, (size_t)8 + 2 * (size_t)rgrid));
+  double* d_stat = h->d_cov_stat;         // [0] deficient points, [4..6] diagonal min / max / bad
+  double* d_rpart = h->d_cov_stat + 8;    // the rank kernel's work-group partials
+
+  // ---- undamped linearisation at the current parameters ----
+  HIP_OK(hipMemsetAsync(h->d_scal + S_XERR, 0, sizeof(double), s));
+  HIP_OK(hipEventRecord(h->cov_ev[0], s));
+  CHECK_RC(eval_jacobian_and_blocks(h, false));
+  k_scale_points<<<grid_for(3 * NP, 256, 1 << 20), 256, 0, s>>>(NP, h->d_V, h->d_scale_p, opt.jacobi_scaling);
+  if (NC > 0) k_scale_cams<<<grid_for(6 * NC, 256, 1 << 20), 256, 0, s>>>(NC, h->ug(), h->d_scale_c, opt.jacobi_scaling);
+  HIP_OK(hipEventRecord(h->cov_ev[1], s));
+  CHECK_RC(read_scalars(h));
+  if (h->h_scal[S_COST_BAD] != 0.0)
+    return set_error(DAB_E_INVALID, "residuals are not finite at the current parameters");
+  const double x_cost = 0.5 * h->h_scal[S_COST];
+  out.cost = x_cost;
+
+  // ---- point factor without LM diagonal, and the point-side rank test ----
+  dab_options lm;
+  dab_options_init(&lm);
+  const StepScalars sc{std::numeric_limits<double>::infinity(), lm.min_lm_diagonal, lm.max_lm_diagonal};
+  HIP_OK(hipMemsetAsync(h->d_flags, 0, sizeof(int) * 4, s));
+  launch_point_factor(s, v, h->d_V, h->d_g, h->d_scale_p, sc, h->d_L, h->d_q, h->d_flags);
+  double* d_ratio = h->d_dp;  // [NP] of the step buffer (scratch between LM steps)
+  launch_cov_point_rank(s, NP, h->d_V, h->d_scale_p, opt.min_pivot_ratio, d_ratio, d_rpart, rgrid);
+  launch_final_sum(s, rgrid, 1, d_rpart, d_stat);
+  CHECK_RC(h->allreduce(d_stat, 1, ncclMax));  // every rank takes the same exit
+  double hstat[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  std::vector<double> hmin((size_t)rgrid);
+  HIP_OK(hipMemcpyAsync(hstat, d_stat, sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(hmin.data(), d_rpart + rgrid, sizeof(double) * (size_t)rgrid, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  CHECK_RC(p2p_check(h->p2p_main));
+  if (NP > 0) out.point_pivot_ratio_min = *std::min_element(hmin.begin(), hmin.end());
+  auto finish = [&](hipEvent_t last) -> int {
+    float ms = 0.f;
+    HIP_OK(hipEventSynchronize(last));
+    HIP_OK(hipEventElapsedTime(&ms, h->cov_ev[0], h->cov_ev[1]));
+    out.evaluate_ms = ms;
+    if (last != h->cov_ev[1]) {
+      HIP_OK(hipEventElapsedTime(&ms, h->cov_ev[1], h->cov_ev[2]));
+      out.factor_ms = ms;
+    }
+    if (last == h->cov_ev[4]) {
+      HIP_OK(hipEventElapsedTime(&ms, h->cov_ev[2], h->cov_ev[3]));
+      out.inverse_ms = ms;
+      HIP_OK(hipEventElapsedTime(&ms, h->cov_ev[3], h->cov_ev[4]));
+      out.points_ms = ms;
+    }
+    if (info) *info = out;
+    return 0;
+  };
+  if (hstat[0] > 0.0) {
+    out.status = DAB_COV_RANK_DEFICIENT;
+    out.deficient_points = (int)hstat[0];
+    std::vector<double> ratio((size_t)NP);
+    if (NP > 0) HIP_OK(hipMemcpy(ratio.data(), d_ratio, sizeof(double) * (size_t)NP, hipMemcpyDeviceToHost));
+    int first = -1;
+    for (int i = 0; i < NP; ++i)
+      if (!(ratio[i] > opt.min_pivot_ratio) && (first < 0 || h->pt_of[i] < first)) first = h->pt_of[i];
+    out.first_deficient_point = first;
+    return finish(h->cov_ev[1]);
+  }
+
+  // ---- S and its factor (the exact step's assembly, unchanged) ----
+  if (NC > 0 && h->schur_tiles) {
+    SchurTiles a = h->tiles;
+    a.kq = 0;
+    if (x_cost > 0.0 && std::isfinite(x_cost)) {
+      int e2;
+      (void)std::frexp(2.0 * x_cost, &e2);
+      a.kq = (e2 + 1) >> 1;
+    }
+    launch_schur_scale(s, NC, h->ug(), h->d_scale_c, h->d_kx);
+    HIP_OK(hipMemsetAsync(h->d_rfx, 0, sizeof(unsigned long long) * 6 * (size_t)NC, s));
+    launch_schur_y(s, v, h->d_points, h->d_camtab, h->d_L, h->d_q, h->d_scale_c, a, h->d_yrec, h->d_rfx);
+    launch_schur_tiles(s, h->d_yrec, a, NC);
+    launch_schur_sum_tiles(s, a, h->d_sblk);
+    CHECK_RC(h->allreduce(h->d_sblk, (size_t)a.nelem, ncclSum));
+    CHECK_RC(h->allreduce_u64(reinterpret_cast<uint64_t*>(h->d_rfx), (size_t)6 * NC));
+    HIP_OK(hipMemsetAsync(h->d_S, 0, sizeof(double) * (size_t)(n + 1) * h->lds, s));
+    launch_schur_unpack(s, NC, h->d_sblk, h->d_rfx, h->d_kx, a.kq, h->d_S, h->lds, h->ybc());
+    launch_s_add_u(s, NC, h->ug(), h->ncross, h->d_cross_cam, h->Ux(), h->d_scale_c, sc, h->ybc(), h->d_S, h->lds);
+    // the point kernel reads per-entry records: the tile path keeps per-(point, camera) sums only
+    if (!h->d_Yrec) CHECK_RC(h->dev.alloc(&h->d_Yrec, (size_t)kYRec * std::max(1, h->NE)));
+    if (point_cov)
+      launch_entry_y(s, v, h->d_points, h->d_camtab, h->d_scale_c, h->d_L, YBufs{h->d_Y, h->d_Yp, false}, false,
+                     h->d_Yrec);
+  } else if (NC > 0) {
+    const YBufs yb{h->d_Y, h->d_Yp, false};
+    launch_entry_y(s, v, h->d_points, h->d_camtab, h->d_scale_c, h->d_L, yb, false, h->d_Yrec);
+    const bool direct = h->world == 1;
+    launch_s_blocks(s, h->nblk, h->d_blk_pair_beg, h->d_pairs, nullptr, h->NE, h->packed(), h->d_Yrec,
+                    direct ? h->d_S : nullptr, h->lds, h->d_blk_cam, h->nzero, h->d_blk_zero);
+    launch_cam_rhs_partial(s, v, h->nchunk, h->d_chunk_beg, h->d_Yrec, h->d_q, h->d_partial, true);
+    launch_seg_final(s, NC, 6, h->d_seg_chunk, h->d_partial, h->ybc(), h->max_seg_chunks);
+    if (direct) {
+      launch_s_add_u(s, NC, h->ug(), h->ncross, h->d_cross_cam, h->Ux(), h->d_scale_c, sc, h->ybc(), h->d_S, h->lds);
+    } else {
+      CHECK_RC(h->allreduce(h->d_spack, h->spack_count(), ncclSum));
+      launch_s_unpack(s, NC, h->nblk, h->d_blk_cam, h->packed(), h->ug(), h->ncross, h->d_cross_cam, h->Ux(),
+                      h->d_scale_c, sc, h->ybc(), h->d_S, h->lds);
+    }
+  }
+  if (NC > 0) {
+    if (chol_factor_solve(h->chol, s, n, h->d_S, h->lds, h->d_yc, h->d_flags + 1) != 0)
+      return set_error(DAB_E_DEVICE, "dense Cholesky launch failed");
+    launch_cov_diag_minmax(s, n, chol_diag_blocks(h->chol), d_stat + 4);
+  }
+  HIP_OK(hipEventRecord(h->cov_ev[2], s));
+  HIP_OK(hipMemcpyAsync(hstat + 4, d_stat + 4, sizeof(double) * 3, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(h->h_flags, h->d_flags, sizeof(int) * 4, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  CHECK_RC(p2p_check(h->p2p_main));
+  if (h->h_flags[0] != 0) return set_error(DAB_E_DEVICE, "point factor failed after the rank test passed");
+  if (NC > 0) {
+    if (h->h_flags[1] & 2)
+      return set_error(DAB_E_DEVICE, "dense Cholesky: a bounded wait between work-groups timed out");
+    const bool flagged = h->h_flags[1] != 0 || hstat[6] != 0.0;
+    out.camera_pivot_ratio = flagged ? 0.0 : hstat[4] / hstat[5];
+    if (!(out.camera_pivot_ratio > opt.min_pivot_ratio)) {
+      out.status = DAB_COV_RANK_DEFICIENT;
+      return finish(h->cov_ev[2]);
+    }
+  }
+  if (!point_cov && !ext_cov && !ext_full) return finish(h->cov_ev[2]);  // the size / rank query
+
+  // ---- C = S^-1 from the factor, the point blocks, the unscaled camera part ----
+  const bool want_c = NC > 0 && (point_cov || ext_cov || ext_full);
+  if (want_c) {
+    if (!h->d_covZ) CHECK_RC(h->dev.alloc(&h->d_covZ, (size_t)n * h->lds));
+    launch_cov_inverse(s, n, h->d_S, h->lds, chol_diag_blocks(h->chol), h->d_covZ, h->lds, h->d_S, h->lds);
+  }
+  HIP_OK(hipEventRecord(h->cov_ev[3], s));
+  if (point_cov) {
+    if (!h->d_cov_pts) CHECK_RC(h->dev.alloc(&h->d_cov_pts, (size_t)6 * std::max(1, NP)));
+    if (!h->d_cov_idx) CHECK_RC(h->dev.alloc(&h->d_cov_idx, (size_t)std::max(1, h->NE) + (size_t)std::max(1, NP)));
+    // d_Y (the step's camera-major Y planes, unused on this route) takes the merged records
+    launch_cov_points(s, v, NC > 0 && h->NE > 0, h->d_L, h->d_Yrec, h->d_Y, h->d_cov_idx,
+                      h->d_cov_idx + std::max(1, h->NE), h->d_S, h->lds, h->d_cov_pts);
+  }
+  HIP_OK(hipEventRecord(h->cov_ev[4], s));
+  double* d_ext21 = nullptr;
+  if (want_c && (ext_cov || ext_full)) {
+    if (ext_cov) {
+      if (!h->d_cov_ext) CHECK_RC(h->dev.alloc(&h->d_cov_ext, (size_t)21 * NC));
+      d_ext21 = h->d_cov_ext;
+    }
+    launch_cov_unscale(s, NC, h->d_scale_c, h->d_S, h->lds, d_ext21);
+  }
+  std::vector<double> hp;
+  if (point_cov && NP > 0) {
+    hp.resize((size_t)6 * NP);
+    HIP_OK(hipMemcpyAsync(hp.data(), h->d_cov_pts, hp.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  HIP_OK(hipStreamSynchronize(s));
+  // every array is written from here on, after the last check that can fail
+  if (point_cov) {
+    const size_t npts = (size_t)h->prob.num_points;
+    std::fill(point_cov, point_cov + 6 * npts, std::numeric_limits<double>::quiet_NaN());
+    for (int i = 0; i < NP; ++i)
+      std::memcpy(point_cov + 6 * (size_t)h->pt_of[i], hp.data() + 6 * (size_t)i, 6 * sizeof(double));
+  }
+  if (ext_cov && NC > 0)
+    HIP_OK(hipMemcpy(ext_cov, d_ext21, sizeof(double) * 21 * (size_t)NC, hipMemcpyDeviceToHost));
+  if (ext_full && NC > 0)
+    HIP_OK(hipMemcpy2D(ext_full, (size_t)n * sizeof(double), h->d_S, (size_t)h->lds * sizeof(double),
+                       (size_t)n * sizeof(double), (size_t)n, hipMemcpyDeviceToHost));
+  return finish(h->cov_ev[4]);
+}
+extern "C" int dab_covariance(dab_handle* h, const dab_covariance_options* opt, double* point_cov, double* ext_cov,
+                              double* ext_full, dab_covariance_info* info) {
+  const int rc = covariance_impl(h, opt, point_cov, ext_cov, ext_full, info);
+  if (h) CHECK_RC(guard_fail(h, "dab_covariance"));
+  return rc;
 }
 
 // ------------------------------------------------------------------------------------

@@ -19,6 +19,13 @@ void clear_error() { g_last_error.clear(); }
 extern "C" const char* dab_last_error(void) { return g_last_error.c_str(); }
 extern "C" int dab_abi_version(void) { return DAB_ABI_VERSION; }
 
+extern "C" void dab_covariance_options_init(dab_covariance_options* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof(*o));
+  o->min_pivot_ratio = 1e-10;  // between the gauge-free (<= 2.5e-12) and well-posed (>= 1.1e-2) ratios
+  o->jacobi_scaling = 1;
+}
+
 extern "C" void dab_options_init(dab_options* o) {
   if (!o) return;
   std::memset(o, 0, sizeof(*o));

@@ -256,6 +256,54 @@ Point3d::~Point3d() {
 
 DeepArcManager::~DeepArcManager() { clear(); }
 
+DeepArcManager::Covariance DeepArcManager::covariance(const std::vector<int>& extra_const, bool freeze_camera,
+                                                      bool full) {
+  DabScene scene;
+  scene.build(*this, freeze_camera);
+  for (int e : extra_const) {
+    if (e < 0 || (size_t)e >= scene.ext_const.size()) throw "covariance: extra constant extrinsic out of range";
+    scene.ext_const[e] = 1;  // the problem points at this array
+  }
+  DabHandle dh;
+  dab_check(dab_set_loss(dh.h, loss_type_, loss_scale_));
+  dab_check(dab_set_problem(dh.h, &scene.problem));
+  dab_covariance_info info{};
+  dab_check(dab_covariance(dh.h, nullptr, nullptr, nullptr, nullptr, &info));
+  Covariance out;
+  const size_t nfe = (size_t)info.num_free_ext;
+  if (info.status == DAB_COV_OK) {
+    out.point_cov.resize(6 * point3d_.size());
+    out.ext_cov.resize(21 * nfe);
+    if (full) out.ext_full.resize(36 * nfe * nfe);
+    dab_check(dab_covariance(dh.h, nullptr, out.point_cov.data(), out.ext_cov.data(),
+                             full ? out.ext_full.data() : nullptr, &info));
+    // the free extrinsics in ascending index: referenced by a block and not constant
+    std::vector<char> used(scene.ext_const.size(), 0);
+    for (size_t o = 0; o < scene.obs_ext0.size(); ++o) {
+      used[scene.obs_ext0[o]] = 1;
+      if (scene.obs_ext1[o] >= 0) used[scene.obs_ext1[o]] = 1;
+    }
+    for (size_t e = 0; e < used.size() && !freeze_camera; ++e) {
+      if (!used[e] || scene.ext_const[e]) continue;
+      const bool ring = share_extrinsic_ && (int)e >= arc_size_;
+      out.ext_index.push_back((int)e);
+      out.ext_kind.push_back(ring ? 'r' : 'a');
+      out.ext_position.push_back(ring ? (int)e - arc_size_ + 1 : (int)e);
+    }
+    if (out.ext_index.size() != nfe) throw "covariance: free extrinsic count mismatch";
+  }
+  out.ok = info.status == DAB_COV_OK;
+  out.status = info.status;
+  out.first_deficient_point = info.first_deficient_point;
+  out.deficient_points = info.deficient_points;
+  out.point_pivot_ratio_min = info.point_pivot_ratio_min;
+  out.camera_pivot_ratio = info.camera_pivot_ratio;
+  out.cost = info.cost;
+  out.num_residuals = info.num_residuals;
+  out.num_parameters = info.num_parameters;
+  return out;
+}
+
 DabSession& DeepArcManager::dabSession() {
   if (!session_) session_.reset(new DabSession());
   return *session_;

@@ -58,6 +58,28 @@ class DeepArcManager {
   int lossType() const { return loss_type_; }
   double lossScale() const { return loss_scale_; }
 
+  // Covariance of the current scene at its current parameters (dab_covariance in dab.h: Sigma =
+  // (J^T J)^-1 under this manager's loss, no sigma^2 factor; ceres::Covariance). The reference's
+  // gauge rule (only the (0,0) block's extrinsic constant, sfm.cc:50-53) leaves the rig's global
+  // scale free, and the call then reports rank deficiency instead of numbers: name one more
+  // extrinsic in extra_const to fix the scale. Its own handle: the resident problem of solve() /
+  // filterPoint3d() is not touched.
+  struct Covariance {
+    bool ok = false;                // false: rank deficient (see status), the arrays are empty
+    int status = 0;                 // DAB_COV_*
+    int first_deficient_point = -1, deficient_points = 0;  // index in point3ds()
+    double point_pivot_ratio_min = 0, camera_pivot_ratio = 0;
+    double cost = 0;
+    int num_residuals = 0, num_parameters = 0;
+    std::vector<double> point_cov;  // [point3ds()->size()][6] upper-packed, point3ds() order (NaN: no block)
+    std::vector<double> ext_cov;    // [free extrinsics][21] upper-packed
+    std::vector<double> ext_full;   // [6 nfe][6 nfe] when asked for
+    std::vector<int> ext_index;     // per row of ext_cov: index in extrinsics()
+    std::vector<char> ext_kind;     // 'a' arc (or a plain extrinsic in non-shared mode) | 'r' ring
+    std::vector<int> ext_position;  // arc or ring position of that extrinsic
+  };
+  Covariance covariance(const std::vector<int>& extra_const = {}, bool freeze_camera = false, bool full = false);
+
  private:
   std::unique_ptr<DabSession> session_;
   unsigned long long structure_version_ = 0;

@@ -3,6 +3,7 @@
 #include <exception>
 #include <string>
 #include <unordered_map>
+#include <vector>
 
 #include "../../include/deeparc_host.h"
 #include "DeepArcManager.hh"
@@ -139,6 +140,38 @@ int dam_set_loss(dam_manager* m, int32_t loss_type, double scale) {
     if (loss_type != DAB_LOSS_TRIVIAL && !(scale > 0.0 && scale <= 1.7976931348623157e308))
       throw "loss scale must be finite and > 0";
     m->m.setLoss(loss_type, scale);
+  });
+}
+
+int dam_covariance(dam_manager* m, const int32_t* extra_const, int32_t n_extra, int32_t freeze_camera,
+                   double* point_cov, double* ext_cov, double* ext_full, int32_t* ext_label,
+                   dab_covariance_info* info) {
+  return guarded([&] {
+    if (!m) throw "null manager";
+    std::vector<int> extra(extra_const, extra_const + (extra_const ? n_extra : 0));
+    const DeepArcManager::Covariance c = m->m.covariance(extra, freeze_camera != 0, ext_full != nullptr);
+    if (info) {
+      *info = dab_covariance_info{};
+      info->status = c.status;
+      info->num_free_ext = c.ok ? (int32_t)c.ext_index.size() : 0;
+      info->num_free_points = 0;
+      info->first_deficient_point = c.first_deficient_point;
+      info->deficient_points = c.deficient_points;
+      info->point_pivot_ratio_min = c.point_pivot_ratio_min;
+      info->camera_pivot_ratio = c.camera_pivot_ratio;
+      info->cost = c.cost;
+      info->num_residuals = c.num_residuals;
+      info->num_parameters = c.num_parameters;
+    }
+    if (!c.ok) return;
+    if (point_cov) std::memcpy(point_cov, c.point_cov.data(), c.point_cov.size() * sizeof(double));
+    if (ext_cov) std::memcpy(ext_cov, c.ext_cov.data(), c.ext_cov.size() * sizeof(double));
+    if (ext_full) std::memcpy(ext_full, c.ext_full.data(), c.ext_full.size() * sizeof(double));
+    for (size_t i = 0; ext_label && i < c.ext_index.size(); ++i) {
+      ext_label[3 * i] = c.ext_index[i];
+      ext_label[3 * i + 1] = c.ext_kind[i] == 'r' ? 1 : 0;
+      ext_label[3 * i + 2] = c.ext_position[i];
+    }
   });
 }
 

@@ -45,6 +45,8 @@ SIGNATURES = {
     "dam_solve": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                             C.POINTER(_abi.DabSummary)]),
     "dam_set_loss": (C.c_int, [C.c_void_p, C.c_int32, C.c_double]),
+    "dam_covariance": (C.c_int, [C.c_void_p, _ip, C.c_int32, C.c_int32, _dp, _dp, _dp, _ip,
+                                 C.POINTER(_abi.DabCovarianceInfo)]),
     "dam_filter": (C.c_int, [C.c_void_p, C.c_double, _dp, C.c_double]),
     "dam_camera_centers": (C.c_int, [C.c_void_p, _dp, C.c_int32, _ip]),
     "dam_fit_hemisphere": (C.c_int, [_dp, C.c_int32, _dp, _dp, C.c_int32]),
@@ -143,6 +145,33 @@ class DeepArcManager:
         """Robust loss of every later solve() of this manager (dam_set_loss): kind as
         core.Solver.set_loss, e.g. set_loss("cauchy", 0.5) for `new ceres::CauchyLoss(0.5)`."""
         _check(self.lib.dam_set_loss(self.h, _abi.loss_kind(kind), float(scale)))
+
+    def covariance(self, extra_const=(), freeze_camera=False, full=False):
+        """DeepArcManager::covariance (dam_covariance): the covariance of the current scene at its
+        current parameters under the manager's loss, shaped like core.Solver.covariance: `info`,
+        `point_cov` (points, 3, 3) in points() order, `ext_cov` (nfe, 6, 6) with `ext_index` and
+        `ext_label` rows ("arc" | "ring", position), `ext_full` when full. extra_const: extrinsic
+        indices held constant beside the gauge rule's (one more fixes the rig's scale gauge);
+        the arrays are None when info["status"] is "RANK_DEFICIENT"."""
+        from .core import _unpack_sym
+        ex = np.ascontiguousarray(list(extra_const), np.int32)
+        info = _abi.DabCovarianceInfo()
+
+        def call(pc, ec, ef, lab):
+            _check(self.lib.dam_covariance(self.h, _p(ex, C.c_int32) if ex.size else None, int(ex.size),
+                                           int(bool(freeze_camera)), pc, ec, ef, lab, C.byref(info)))
+        call(None, None, None, None)
+        d = {k: getattr(info, k) for k, _ in _abi.DabCovarianceInfo._fields_}
+        d["status"] = _abi.COV_STATUS.get(info.status, str(info.status))
+        if info.status != 0:
+            return dict(info=d, point_cov=None, ext_cov=None, ext_index=None, ext_label=None, ext_full=None)
+        nfe, npts = info.num_free_ext, self.sizes()["points"]
+        pc, ec = np.zeros((npts, 6)), np.zeros((nfe, 21))
+        ef = np.zeros((6 * nfe, 6 * nfe)) if full else None
+        lab = np.zeros((nfe, 3), np.int32)
+        call(_p(pc, C.c_double), _p(ec, C.c_double), _p(ef, C.c_double) if full else None, _p(lab, C.c_int32))
+        return dict(info=d, point_cov=_unpack_sym(pc, 3), ext_cov=_unpack_sym(ec, 6), ext_index=lab[:, 0].copy(),
+                    ext_label=[("ring" if k else "arc", int(p)) for _, k, p in lab], ext_full=ef)
 
     def filterPoint3d(self, error_boundary, hemisphere_center, hemisphere_radius):  # noqa: N802
         c = np.ascontiguousarray(hemisphere_center, np.float64)

@@ -285,6 +285,80 @@ int dab_eval_jacobians(dab_handle* h, double* residuals, double* jacobians);
 int dab_filter(dab_handle* h, double error_boundary, const double center[3], double radius,
                uint8_t* obs_keep, uint8_t* point_keep, int32_t* n_obs_kept, int32_t* n_points_kept);
 
+/* ---- covariance at the current parameters (ceres::Covariance) -----------------------------
+ * J = the Jacobian of the handle's problem at the parameters now on the handle, over the free
+ * parameters only (referenced points, then referenced non-constant extrinsics, as
+ * dab_summary.num_parameters counts them); under a non-trivial loss its rows are scaled by
+ * sqrt(rho') exactly as dab_solve scales them. The covariance is Sigma = (J^T J)^-1, undamped
+ * and without a sigma^2 factor: info->cost and the degrees of freedom (num_residuals -
+ * num_parameters) let the caller multiply by 2 cost / dof. Returned are the diagonal blocks of
+ * Sigma and, optionally, its whole camera part:
+ *   point_cov [num_points][6]   upper-packed 00 01 02 11 12 22, caller's point order; rows of
+ *                               points referenced by no observation on this rank are NaN
+ *   ext_cov   [num_free_ext][21] upper-packed 6x6 per free extrinsic, ascending extrinsic index
+ *                               (dab_bench_get_blocks' order)
+ *   ext_full  [6 nfe][6 nfe]    row-major, both triangles (bitwise symmetric; its diagonal
+ *                               blocks equal ext_cov bitwise)
+ * Every array may be NULL; with all three NULL the call fills info (sizes, rank test) only.
+ * With freeze_camera, or no free extrinsic, Sigma_pp = V^-1 and the camera arrays are empty.
+ *
+ * Route: always the exact one, all fp64, whatever solver the handle last used and whatever
+ * pcg_fp32 said: evaluation pass, point factor without LM diagonal, explicit Schur complement
+ * S (pair tables or block tiles, built on first use as dab_solve does for EXPLICIT_SCHUR),
+ * dense Cholesky, C = S^-1 from the factor, Sigma_pp = PU (I + sum Y^T C Y) PU^T, all in the
+ * Jacobi-scaled variables (jacobi_scaling) and unscaled at the end. The first call that needs C
+ * allocates a second n x n buffer (n = 6 num_free_ext; DAB_E_NOMEM when it cannot), freed by
+ * dab_set_problem and dab_destroy. The handle's parameters, loss and problem are unchanged: a
+ * dab_solve after it gives bitwise the trajectory it would have given without it, and two calls
+ * in a row give bitwise the same arrays.
+ *
+ * Rank test, fail closed. J^T J must be invertible, and for this project's problems it often
+ * is not: the reference's own gauge rule (only arc 0 constant, sfm.cc:50-53) leaves the global
+ * scale of the rig free (J^T J has exactly one singular value at ~1e-11 of the largest; its null
+ * vector is translations plus points), and so does a BAL-shaped problem with one constant
+ * camera. A point with a single observation has a rank-2 block. The call tests
+ *   - every point's scaled undamped 3x3 block: min / max pivot of its Cholesky must be
+ *     > min_pivot_ratio;
+ *   - the camera system: the dense factor must not flag a non-positive pivot, and min / max of
+ *     its squared diagonal must be > min_pivot_ratio.
+ * Measured ratios: >= 9.9e-3 on well-posed problems, |ratio| <= 2.5e-12 on gauge-free ones,
+ * <= 5e-15 for single-observation points; the default 1e-10 sits between. A failure returns
+ * DAB_OK with info->status = DAB_COV_RANK_DEFICIENT and writes no array; the point side fills
+ * first_deficient_point / deficient_points, the camera side camera_pivot_ratio (0 when the
+ * factor met a non-positive pivot). Deficient points are not skipped: their observations would
+ * still sit in U and S would be overconfident. Remedies: drop such points from the problem
+ * (Problem.subset in the Python layer), and fix the scale gauge with one more constant extrinsic
+ * (ext_const) beside the reference's arc 0 / camera 0.
+ *
+ * Multi-rank handles: every rank calls it. S is all-reduced as in the exact step, every rank
+ * inverts its own copy (identical camera arrays) and gets the covariances of its own shard's
+ * points; the point-side deficiency count is max-reduced, so every rank returns the same status.
+ * Errors: DAB_E_INVALID for a null handle (checked before any device use), a min_pivot_ratio
+ * that is not finite and > 0, or a null info together with null arrays; DAB_E_STATE before
+ * dab_set_problem. */
+#define DAB_COV_OK 0
+#define DAB_COV_RANK_DEFICIENT 1
+typedef struct dab_covariance_options {
+  double min_pivot_ratio;   /* 1e-10; see the rank test */
+  int32_t jacobi_scaling;   /* 1 */
+  int32_t reserved;
+} dab_covariance_options;
+void dab_covariance_options_init(dab_covariance_options* opt);
+
+typedef struct dab_covariance_info {
+  int32_t status;                 /* DAB_COV_OK | DAB_COV_RANK_DEFICIENT */
+  int32_t num_free_ext, num_free_points;
+  int32_t first_deficient_point;  /* caller's point index (the lowest on this rank), or -1 */
+  int32_t deficient_points;       /* count (max over the ranks) */
+  int32_t schur_assembly;         /* DAB_SCHUR_PAIRS | DAB_SCHUR_TILES */
+  double point_pivot_ratio_min, camera_pivot_ratio;  /* what the rank test saw */
+  double cost; int32_t num_residuals, num_parameters;
+  double evaluate_ms, factor_ms, inverse_ms, points_ms;  /* device times, HIP events */
+} dab_covariance_info;
+
+int dab_covariance(dab_handle* h, const dab_covariance_options* opt /* NULL = defaults */,
+                   double* point_cov, double* ext_cov, double* ext_full, dab_covariance_info* info);
+
 /* Dense SPD solve A x = b on the handle's device with the library's blocked Cholesky (the
  * reduced-camera-system factorisation of DAB_LINEAR_SOLVER_EXPLICIT_SCHUR; Eigen LLT in
  * Ceres' DENSE_SCHUR). A: n x n row-major, only the lower triangle is read. factor_ms

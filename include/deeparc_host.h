@@ -13,6 +13,7 @@
  *   dam_camera_centers                     DeepArcManager::getCameraCenter, DeepArcManager.cc:501-518
  *   dam_fit_hemisphere                     the HemisphereRadius fit, sfm.cc:83-101
  *   dam_run_pipeline                       main(), sfm.cc:79-129
+ *   dam_covariance                         (no reference call: ceres::Covariance after Solve)
  * Return 0 on success, negative on error (message in dam_last_error; the C++ API throws
  * const char* like the reference).
  */
@@ -52,6 +53,16 @@ int dam_solve(dam_manager* m, int32_t max_iteration, int32_t max_second, int32_t
  * manager; the default is the reference's NULL loss (sfm.cc:48-49). A bad type or scale
  * returns an error and leaves the loss as it was. dam_filter keeps the bare residual. */
 int dam_set_loss(dam_manager* m, int32_t loss_type, double scale);
+/* DeepArcManager::covariance: dab_covariance (dab.h) of the manager's current scene at its
+ * current parameters, under the manager's loss. extra_const[n_extra]: extrinsic indices held
+ * constant beside the gauge rule's; the reference's rule leaves the rig's global scale free
+ * (status DAB_COV_RANK_DEFICIENT), one more constant extrinsic fixes it. point_cov [n_points][6]
+ * in point order; ext_cov [nfe][21]; ext_full [6 nfe][6 nfe]; ext_label [nfe][3] = (index in the
+ * extrinsic list, 0 arc | 1 ring, arc or ring position). Every array may be NULL: query
+ * info->num_free_ext first. A rank-deficient scene returns 0 and writes no array. */
+int dam_covariance(dam_manager* m, const int32_t* extra_const, int32_t n_extra, int32_t freeze_camera,
+                   double* point_cov, double* ext_cov, double* ext_full, int32_t* ext_label,
+                   dab_covariance_info* info);
 int dam_filter(dam_manager* m, double error_boundary, const double center[3], double radius);
 /* out [capacity][3]; *count = number of centres (may exceed capacity) */
 int dam_camera_centers(dam_manager* m, double* out, int32_t capacity, int32_t* count);

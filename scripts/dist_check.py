@@ -8,6 +8,9 @@ Schur and PCG). With --device D every rank uses device D (ranks sharing one GPU;
 refuses that, so pair it with --host-collective, which stages the library's collectives
 through gloo and exercises every other part of the sharded path). --loss kind:scale sets a
 robust loss (dab_set_loss) on every rank's handle and on the single handle it is compared with.
+--covariance checks dab_covariance instead: every rank calls it on its shard after the solve, and
+rank 0 compares the camera arrays across the ranks (bitwise) and, with every owner's point rows,
+against a single handle at the same parameters.
 """
 import argparse
 import json
@@ -49,6 +52,12 @@ def main():
                     "(DAB_EVAL_SIDE=7): every rank's dab_solve must fail with the timeout, none may hang")
     ap.add_argument("--loss", default="", help="robust loss kind:scale (huber | soft_l1 | cauchy, e.g. "
                     "cauchy:0.5), set on every rank's handle and on the single-handle comparison")
+    ap.add_argument("--covariance", action="store_true",
+                    help="after the solve (--iters LM iterations of the exact step; 0 = none) every rank calls "
+                    "dab_covariance: the camera arrays must be bitwise equal across the ranks and, like every "
+                    "owner's point rows, within --cov-tol of a single handle at the same parameters")
+    ap.add_argument("--cov-tol", type=float, default=1e-9,
+                    help="--covariance: bound on max |difference| / max |Sigma| against the single handle")
     a = ap.parse_args()
     loss = None
     if a.loss:
@@ -95,6 +104,65 @@ def main():
             ok = int(failed.item()) == world and sched == 2
             sys.stdout.write(f"DIST_CHECK {'OK' if ok else 'FAIL'} timeout: {int(failed.item())}/{world} ranks "
                              f"failed closed, eval schedule {sched}, rank 0: {msg!r}\n")
+            sys.stdout.flush()
+        dist.destroy_process_group()
+        return
+
+    if a.covariance:
+        if a.config:
+            glob = pkg.synth(**pkg.CONFIGS[a.config])
+        else:  # 40 cameras, two of them constant: the scale gauge is fixed, J has full rank
+            glob = pkg.synth(kind=0, num_cameras=40, num_points=200, obs_per_point=8, seed=5)
+        glob.ext_const[1] = 1
+        owner = glob.point_owner(world)
+        mine = glob.copy().shard(rank, world)
+        s = pkg.Solver(dev, rank, world, uid, host_allreduce=gloo_allreduce if a.host_collective else None)
+        if loss:
+            s.set_loss(*loss)
+        s.set_problem(mine)
+        if a.iters > 0:
+            s.solve(pkg.options(max_num_iterations=a.iters, linear_solver_type=pkg.DAB_LINEAR_SOLVER_EXPLICIT_SCHUR))
+        cov = s.covariance(full=True)
+        s.close()
+        ok_here = cov["info"]["status"] == "OK"
+        status = torch.tensor([1 if ok_here else 0], dtype=torch.int32)
+        dist.all_reduce(status)
+        nfe = cov["info"]["num_free_ext"]
+        own = (owner == rank)
+        pts = torch.from_numpy(np.where(own[:, None], mine.points, 0.0))
+        dist.all_reduce(pts)
+        full = cov["ext_full"] if ok_here else np.zeros((6 * nfe, 6 * nfe))
+        blocks = cov["ext_cov"] if ok_here else np.zeros((nfe, 6, 6))
+        hi, lo = torch.from_numpy(full.copy()), torch.from_numpy(full.copy())
+        dist.all_reduce(hi, op=dist.ReduceOp.MAX)
+        dist.all_reduce(lo, op=dist.ReduceOp.MIN)
+        bhi, blo = torch.from_numpy(blocks.copy()), torch.from_numpy(blocks.copy())
+        dist.all_reduce(bhi, op=dist.ReduceOp.MAX)
+        dist.all_reduce(blo, op=dist.ReduceOp.MIN)
+        pc = cov["point_cov"] if ok_here else np.zeros((glob.points.shape[0], 3, 3))
+        pc = torch.from_numpy(np.where(own[:, None, None], pc, 0.0))  # every owner's rows (the others' are NaN)
+        dist.all_reduce(pc)
+        if rank == 0:
+            g1 = glob.copy()
+            g1.points[:] = pts.numpy()
+            g1.ext[:] = mine.ext
+            s1 = pkg.Solver(dev)
+            if loss:
+                s1.set_loss(*loss)
+            s1.set_problem(g1)
+            c1 = s1.covariance(full=True)
+            s1.close()
+            res = dict(ranks_ok=int(status.item()), single=c1["info"]["status"],
+                       ranks_equal=bool(torch.equal(hi, lo) and torch.equal(bhi, blo)))
+            good = res["ranks_ok"] == world and res["single"] == "OK" and res["ranks_equal"]
+            if good:
+                m = max(float(np.abs(c1["ext_full"]).max()), float(np.abs(c1["point_cov"]).max()))
+                res.update(m=m, ext_full_err=float(np.abs(hi.numpy() - c1["ext_full"]).max()),
+                           ext_cov_err=float(np.abs(bhi.numpy() - c1["ext_cov"]).max()),
+                           point_cov_err=float(np.abs(pc.numpy() - c1["point_cov"]).max()), tol=a.cov_tol * m)
+                good = max(res["ext_full_err"], res["ext_cov_err"], res["point_cov_err"]) <= a.cov_tol * m
+            print(json.dumps(res, indent=1))
+            sys.stdout.write("DIST_CHECK " + ("OK" if good else "FAIL covariance") + "\n")
             sys.stdout.flush()
         dist.destroy_process_group()
         return
