@@ -9,6 +9,7 @@ from ._abi import (DAB_CONVERGENCE, DAB_E_INVALID, DAB_E_UNSUPPORTED, DAB_FAILUR
                    DAB_LOSS_HUBER, DAB_LOSS_SOFT_L1, DAB_LOSS_TRIVIAL, DAB_NO_CONVERGENCE, LIB_PATH,
                    SIGNATURES, load_library, last_error)
 from ._abi import DabCovarianceInfo, DabCovarianceOptions
+from ._abi import DAB_INTR_CENTER, DAB_INTR_DISTORTION, DAB_INTR_FOCAL
 from .core import CONFIGS, Problem, Solver, covariance_options, options, solve, synth, synth_config
 
 __all__ = [
@@ -19,4 +20,5 @@ __all__ = [
     "DAB_LINEAR_SOLVER_EXPLICIT_SCHUR", "DAB_LINEAR_SOLVER_IMPLICIT_SCHUR_PCG", "DAB_LINEAR_SOLVER_AUTO",
     "DAB_LOSS_TRIVIAL", "DAB_LOSS_HUBER", "DAB_LOSS_SOFT_L1", "DAB_LOSS_CAUCHY",
     "DAB_E_INVALID", "DAB_E_UNSUPPORTED",
+    "DAB_INTR_CENTER", "DAB_INTR_FOCAL", "DAB_INTR_DISTORTION",
 ]

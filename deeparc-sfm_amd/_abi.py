@@ -24,6 +24,9 @@ DAB_LOSS_TRIVIAL = 0
 DAB_LOSS_HUBER = 1
 DAB_LOSS_SOFT_L1 = 2
 DAB_LOSS_CAUCHY = 3
+DAB_INTR_CENTER = 1
+DAB_INTR_FOCAL = 2
+DAB_INTR_DISTORTION = 4
 LOSS_KINDS = {"trivial": DAB_LOSS_TRIVIAL, "huber": DAB_LOSS_HUBER, "soft_l1": DAB_LOSS_SOFT_L1,
               "cauchy": DAB_LOSS_CAUCHY}
 
@@ -148,6 +151,12 @@ SIGNATURES = {
     "dab_set_loss": (C.c_int, [C.c_void_p, C.c_int32, C.c_double]),
     "dab_get_loss": (C.c_int, [C.c_void_p, _ip, _dp]),
     "dab_get_parameters": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "dab_set_intrinsics_free": (C.c_int, [C.c_void_p, _u8p]),
+    "dab_get_intrinsics_free": (C.c_int, [C.c_void_p, _u8p, _ip, _ip]),
+    "dab_get_intrinsics": (C.c_int, [C.c_void_p, _dp]),
+    "dab_update_intrinsics": (C.c_int, [C.c_void_p, _dp]),
+    "dab_eval_intrinsic_jacobians": (C.c_int, [C.c_void_p, _dp]),
+    "dab_get_intrinsic_blocks": (C.c_int, [C.c_void_p, _ip, _dp]),
     "dab_covariance_options_init": (None, [C.POINTER(DabCovarianceOptions)]),
     "dab_covariance": (C.c_int, [C.c_void_p, C.POINTER(DabCovarianceOptions), _dp, _dp, _dp,
                                  C.POINTER(DabCovarianceInfo)]),

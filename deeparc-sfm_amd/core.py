@@ -227,6 +227,7 @@ class Solver:
         self.h = h
         self.problem = None
         self._cp = None
+        self._intr_free = False
 
     @staticmethod
     def unique_id():
@@ -250,6 +251,7 @@ class Solver:
         self.problem = problem
         self._cp = problem.as_c()
         check(self.lib.dab_set_problem(self.h, C.byref(self._cp)), self.lib)
+        self._intr_free = False  # dab_set_problem resets the mask
 
     def update_parameters(self, points=None, ext=None):
         check(self.lib.dab_update_parameters(
@@ -269,6 +271,58 @@ class Solver:
         names = {v: n for n, v in _abi.LOSS_KINDS.items()}
         return names[k.value], a.value
 
+    def set_intrinsics_free(self, groups):
+        """Which intrinsic groups the next solve refines (dab_set_intrinsics_free): DAB_INTR_*
+        bits (CENTER 1 | FOCAL 2 | DISTORTION 4), one int for every intrinsic or an array of
+        num_intr; 0 / None = all constant. Set after set_problem, which resets it."""
+        ni = int(self.problem.intr.shape[0])
+        if groups is None:
+            check(self.lib.dab_set_intrinsics_free(self.h, None), self.lib)
+            self._intr_free = False
+            return
+        g = np.asarray(groups)
+        if g.ndim == 0:
+            g = np.full(ni, int(g))
+        if g.shape != (ni,) or (g < 0).any() or (g > 255).any():
+            raise ValueError(f"groups: one int or {ni} values in 0..7")
+        g = np.ascontiguousarray(g, np.uint8)
+        check(self.lib.dab_set_intrinsics_free(self.h, _ptr(g, C.c_uint8)), self.lib)
+        self._intr_free = bool(g.any())
+
+    def get_intrinsics_free(self):
+        """(groups [num_intr] uint8, free intrinsics, free scalars) of the mask on the handle."""
+        g = np.zeros(int(self.problem.intr.shape[0]), np.uint8)
+        nfi, ns = C.c_int32(), C.c_int32()
+        check(self.lib.dab_get_intrinsics_free(self.h, _ptr(g, C.c_uint8), C.byref(nfi), C.byref(ns)), self.lib)
+        return g, nfi.value, ns.value
+
+    def get_intrinsics(self):
+        """The intrinsics on the handle, [num_intr][6] (refined ones after a solve)."""
+        k = np.zeros((int(self.problem.intr.shape[0]), 6))
+        check(self.lib.dab_get_intrinsics(self.h, _ptr(k, C.c_double)), self.lib)
+        return k
+
+    def update_intrinsics(self, intr):
+        k = np.ascontiguousarray(intr, np.float64).reshape(-1, 6)
+        if k.shape[0] != self.problem.intr.shape[0]:
+            raise ValueError("intr: [num_intr][6]")
+        check(self.lib.dab_update_intrinsics(self.h, _ptr(k, C.c_double)), self.lib)
+
+    def intrinsic_jacobians(self):
+        """d r / d (cx, cy, f0, f1, k0, k1) per observation, (num_obs, 2, 6), raw."""
+        J = np.zeros((self.problem.num_obs, 2, 6))
+        check(self.lib.dab_eval_intrinsic_jacobians(self.h, _ptr(J, C.c_double)), self.lib)
+        return J
+
+    def intrinsic_blocks(self):
+        """[U_zz upper 21 | g_z 6] per free intrinsic of the last evaluation (nfi, 27)."""
+        n = C.c_int32()
+        check(self.lib.dab_get_intrinsic_blocks(self.h, C.byref(n), None), self.lib)
+        zg = np.zeros((n.value, 27))
+        if n.value:
+            check(self.lib.dab_get_intrinsic_blocks(self.h, C.byref(n), _ptr(zg, C.c_double)), self.lib)
+        return zg
+
     def solve(self, opts=None, max_records=1024):
         o = opts if opts is not None else options()
         its = (DabIteration * max_records)()
@@ -276,6 +330,10 @@ class Solver:
         s.iterations = C.cast(its, C.POINTER(DabIteration))
         s.iterations_capacity = max_records
         check(self.lib.dab_solve(self.h, C.byref(o), C.byref(s)), self.lib)
+        # dab_problem.intr is const for the library: the refined values are copied here, in place
+        # like points and ext (identical to the problem's own when no intrinsic is free)
+        if self._intr_free:
+            self.problem.intr[...] = self.get_intrinsics()
         return summary_to_dict(s, its)
 
     def covariance(self, points=True, ext=True, full=False, **opts):
@@ -411,11 +469,13 @@ class Solver:
 
 
 def solve(problem, max_iteration=1000, max_second=3600, freeze_camera=False, device=0,
-          verbose=False, loss=None, **opt_kw):
+          verbose=False, loss=None, free_intrinsics=0, **opt_kw):
     """Drop-in for the reference's solve() (src/sfm.cc:31): DENSE_SCHUR-equivalent LM,
     max_num_iterations / max_solver_time_in_seconds as given, parameters updated in place.
     loss: None (the reference's NULL loss, sfm.cc:48) or a (kind, scale) pair such as
-    ("cauchy", 0.5), the `new ceres::CauchyLoss(0.5)` the reference keeps commented out."""
+    ("cauchy", 0.5), the `new ceres::CauchyLoss(0.5)` the reference keeps commented out.
+    free_intrinsics: DAB_INTR_* bits (an int or one per intrinsic) refined with the cameras, the
+    equivalent of deleting sfm.cc:60-62; problem.intr is updated in place."""
     problem.freeze_camera = bool(freeze_camera)
     o = options(max_num_iterations=max_iteration, max_solver_time_in_seconds=float(max_second),
                 minimizer_progress_to_stdout=int(verbose), **opt_kw)
@@ -424,6 +484,8 @@ def solve(problem, max_iteration=1000, max_second=3600, freeze_camera=False, dev
         if loss is not None:
             s.set_loss(*loss)
         s.set_problem(problem)
+        if np.any(np.asarray(free_intrinsics)):
+            s.set_intrinsics_free(free_intrinsics)
         return s.solve(o)
     finally:
         s.close()

@@ -297,6 +297,41 @@ void launch_candidate(hipStream_t s, const DevView& v, const double* points, con
 void launch_grad_points(hipStream_t s, int NP, const double* x, const double* g /*[3][NP]*/,
                         double* partial, int grid);
 
+// ---- free intrinsics in the exact Schur step (dab_set_intrinsics_free) --------------------
+// meta[NI]: x = free intrinsic index or -1; y = active columns (bits 0..5: cx cy f0 f1 k0 k1
+// selected by the mask and present in the model) | columns present in the model << 8 |
+// (nf == 1) << 16. act[nfi]: the active bits by free index. zg[nfi][kIntrRec]: U_zz upper (21) |
+// g_z (6) | observation count. sz[nfi][6]: Jacobi scale, 0 on inactive slots.
+constexpr int kIntrFreeMax = 16;
+constexpr int kIntrRec = 28;
+void launch_intr_jac(hipStream_t s, const DevView& v, const double* points, const double* camtab, const int2* meta,
+                     double* J /*[N slots][2][6]*/);
+int intr_eval_grid(int N);  // partial[grid][nfi * kIntrRec]
+void launch_intr_eval(hipStream_t s, const DevView& v, const double* points, const double* camtab, const int2* meta,
+                      int nfi, double* partial, double* zg);
+void launch_intr_scale(hipStream_t s, int nfi, const double* zg, const int* act, double* sz, int on);
+// bsum[6 nfi][6 NC + 6 nfi + 1] = camera columns | z columns (lower part) | rhs, this rank's sums
+// (partial: groups x that, groups = intr_border_groups)
+int intr_border_groups(int nslice, int NC, int nfi, int* slices_per_group);
+// ptmask[NP]: bit i = the point sees free intrinsic i (launch_intr_ptmask, once per solve). The
+// sums run in LDS rows when they fit (intr_border_lds_fits: small camera sets) and allow_lds,
+// else in the groups' global partials
+void launch_intr_ptmask(hipStream_t s, const DevView& v, const int2* meta, int* ptmask);
+bool intr_border_lds_fits(int NC, int nfi);
+void launch_intr_border(hipStream_t s, const DevView& v, const double* points, const double* camtab,
+                        const double* scale_c, const double* PU, const double* q, const double* sz, const int2* meta,
+                        const int* ptmask, int nfi, double* partial, double* bsum, bool allow_lds = true);
+// rows n .. n + 6 nfi - 1 of S and the rhs tail of row n + 6 nfi
+void launch_intr_scatter(hipStream_t s, int n, int nfi, const double* bsum, const double* zg, const double* sz,
+                         const int* act, StepScalars sc, double* S, int lds);
+void launch_intr_backsub(hipStream_t s, const DevView& v, const double* points, const double* camtab,
+                         const double* PU, const double* sz, const double* yz, const int2* meta, double* dp);
+void launch_intr_candidate(hipStream_t s, int NI, const int2* meta, const double* intr, const double* sz,
+                           const double* yz, const double* zg, double* intr_c, double* dz, double* out /*[5]*/);
+void launch_candidate_z(hipStream_t s, const DevView& v, const double* points, const double* camtab,
+                        const double* delta_p, const double* delta_c, const double* camtab_c, const int2* meta,
+                        const double* dz, const double* intr_c, double* partial, int grid);
+
 // ---- implicit-Schur PCG (dab_pcg.hip) -------------------------------------------------------
 enum { kPcgRunning = 0, kPcgSuccess = 1, kPcgNoConvergence = 2, kPcgFailure = 3 };
 struct PcgState {

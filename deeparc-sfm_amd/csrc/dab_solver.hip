@@ -310,6 +310,8 @@ struct Knobs {
   int tile_minb = 2;        // DAB_TILE_MINB: fewest batches per k_schur_tiles work-group (8 until round 6)
   int p2p = -1;             // DAB_P2P: one-shot xGMI all-reduce of small sums (-1 auto: RCCL handles
                             // only; 1 also on host-staged handles, the one-GPU rehearsal; 0 off)
+  int intr_border_lds = 1;  // DAB_INTR_BORDER_LDS=0: the free-intrinsic border's sums in global memory
+                            // (k_intr_border_g) even where its LDS rows fit
   int setup_host = 0;       // DAB_SETUP_HOST=1: dab_set_problem's host passes instead of the device ones
   int eval_side = 0;        // DAB_EVAL_SIDE: 7 (test) a k_eval_bal frame wait that times out (the pass
                             // must fail with DAB_E_DEVICE on every rank). Builds with -DDAB_ABLATIONS
@@ -342,6 +344,7 @@ struct Knobs {
     get("DAB_P2P", p2p);
     get("DAB_FUSED_TAB", fused_tab);
     get("DAB_SETUP_HOST", setup_host);
+    get("DAB_INTR_BORDER_LDS", intr_border_lds);
     get("DAB_EVAL_SIDE", eval_side);
   }
   // the evaluation side this build accepts from DAB_EVAL_SIDE
@@ -428,6 +431,25 @@ struct dab_handle {
   int nzero = 0;
   int* d_blk_pair_beg = nullptr;
   double* d_intr = nullptr;
+  // free intrinsics (dab_set_intrinsics_free). The mask is state of the handle, reset by
+  // dab_set_problem; the free set is worked out from it at each call that needs it
+  // (intr_free_set): referenced on some rank and at least one active scalar selected.
+  std::vector<uint8_t> intr_mask;         // [NI] requested groups (DAB_INTR_*)
+  std::vector<uint8_t> intr_ref;          // [NI] referenced by an observation (union over ranks once intr_ref_union)
+  bool intr_ref_union = false;
+  std::vector<double> intr_host;          // [NI][6] dab_problem layout: what dab_get_intrinsics fills unused slots from
+  std::vector<int> intr_nf, intr_nk;
+  std::vector<int2> intr_meta;            // host copy of d_intr_meta (kernels.h)
+  int nfi = 0;                            // free intrinsics of the meta now on the device
+  double* d_intr_c = nullptr;             // candidate intrinsics [NI][kIntr]
+  int2* d_intr_meta = nullptr;            // [NI]
+  int* d_intr_act = nullptr;              // [kIntrFreeMax]
+  // [zg nfi*28 | sz 96 | dz 96 | norms 5+3] and the k_intr_eval / k_intr_border partials (lazy)
+  double *d_zg = nullptr, *d_sz = nullptr, *d_dz = nullptr, *d_znorm = nullptr, *d_zpart = nullptr;
+  double *d_bpart = nullptr, *d_bsum = nullptr, *d_Sz = nullptr, *d_yz = nullptr;
+  int* d_ptmask = nullptr;  // [NP] free intrinsics each point sees (k_intr_ptmask, per solve)
+  size_t bpart_cap = 0, Sz_cap = 0;
+  int ldz = 0;
   double *d_points = nullptr, *d_points_c = nullptr, *d_ext = nullptr, *d_ext_c = nullptr;
   double *d_camtab = nullptr, *d_camtab_c = nullptr;
   double* d_r = nullptr;
@@ -2026,6 +2048,238 @@ static int setup_device(dab_handle* h, const dab_problem* p, const std::function
 }
 
 static int set_problem_impl(dab_handle* h, const dab_problem* p);
+// ------------------------------------------------------------------------------------
+// free intrinsics: host state
+// ------------------------------------------------------------------------------------
+// dab_set_problem: keep the problem's intrinsics, nf / nk and which are referenced here; the
+// mask goes back to all-constant (num_intr may have changed) and the device buffers are lazy
+static int intr_setup(dab_handle* h, const dab_problem* p) {
+  const int NI = p->num_intr;
+  h->intr_mask.assign((size_t)NI, 0);
+  h->intr_ref.assign((size_t)NI, 0);
+  h->intr_ref_union = false;
+  for (int o = 0; o < p->num_obs; ++o) h->intr_ref[(size_t)p->obs_intr[o]] = 1;
+  h->intr_host.assign(p->intr, p->intr + 6 * (size_t)NI);
+  h->intr_nf.assign(p->intr_nf, p->intr_nf + NI);
+  h->intr_nk.assign(p->intr_nk, p->intr_nk + NI);
+  h->intr_meta.clear();
+  h->nfi = 0;
+  h->d_intr_c = nullptr;
+  h->d_intr_meta = nullptr;
+  h->d_intr_act = nullptr;
+  h->d_zg = h->d_sz = h->d_dz = h->d_znorm = h->d_zpart = nullptr;
+  h->d_bpart = h->d_bsum = h->d_Sz = h->d_yz = nullptr;
+  h->d_ptmask = nullptr;
+  h->bpart_cap = h->Sz_cap = 0;
+  return 0;
+}
+static bool intr_mask_any(const dab_handle* h) {  // some group requested (and not overridden by freeze_camera)
+  if (h->prob.freeze_camera) return false;
+  for (uint8_t m : h->intr_mask)
+    if (m) return true;
+  return false;
+}
+static int intr_struct_bits(const dab_handle* h, int i) {  // scalars the model of intrinsic i has
+  return 0x07 | (h->intr_nf[i] == 2 ? 0x08 : 0) | (h->intr_nk[i] >= 1 ? 0x10 : 0) | (h->intr_nk[i] >= 2 ? 0x20 : 0);
+}
+static int intr_group_bits(int groups) {
+  return ((groups & DAB_INTR_CENTER) ? 0x03 : 0) | ((groups & DAB_INTR_FOCAL) ? 0x0c : 0) |
+         ((groups & DAB_INTR_DISTORTION) ? 0x30 : 0);
+}
+// The free set of the mask now on the handle -> d_intr_meta / d_intr_act / h->nfi (uploaded
+// when it changed). Collective on a multi-rank handle with a non-empty mask (the referenced
+// union, once per problem). with_mask = false: the all-constant meta (parity calls).
+static int intr_free_set(dab_handle* h, bool with_mask, int* nfi_out, int* nscal_out = nullptr) {
+  const int NI = h->NI;
+  bool any = false;
+  for (int i = 0; i < NI; ++i) any = any || h->intr_mask[(size_t)i] != 0;
+  any = any && with_mask && !h->prob.freeze_camera;
+  if (any && h->coll() && !h->intr_ref_union) {
+    double* d_ref = nullptr;
+    CHECK_RC(h->dev.alloc(&d_ref, (size_t)std::max(1, NI)));
+    std::vector<double> ref((size_t)NI);
+    for (int i = 0; i < NI; ++i) ref[(size_t)i] = h->intr_ref[(size_t)i];
+    HIP_OK(hipMemcpyAsync(d_ref, ref.data(), sizeof(double) * NI, hipMemcpyHostToDevice, h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));
+    CHECK_RC(h->allreduce(d_ref, (size_t)NI, ncclMax));
+    HIP_OK(hipMemcpyAsync(ref.data(), d_ref, sizeof(double) * NI, hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < NI; ++i) h->intr_ref[(size_t)i] = ref[(size_t)i] != 0.0;
+    h->intr_ref_union = true;
+    h->dev.drop(d_ref);
+  }
+  std::vector<int2> meta((size_t)std::max(1, NI), make_int2(-1, 0));
+  int act[kIntrFreeMax] = {0};
+  int nfi = 0, nscal = 0;
+  for (int i = 0; i < NI; ++i) {
+    const int sb = intr_struct_bits(h, i);
+    const int ab = any && h->intr_ref[(size_t)i] ? (sb & intr_group_bits(h->intr_mask[(size_t)i])) : 0;
+    meta[(size_t)i].y = (sb << 8) | (h->intr_nf[i] == 1 ? 1 << 16 : 0);
+    if (ab == 0) continue;
+    meta[(size_t)i].x = nfi;
+    meta[(size_t)i].y |= ab;
+    if (nfi < kIntrFreeMax) act[nfi] = ab;
+    ++nfi;
+    nscal += __builtin_popcount((unsigned)ab);
+  }
+  if (nfi_out) *nfi_out = nfi;
+  if (nscal_out) *nscal_out = nscal;
+  if (nfi > kIntrFreeMax) return 0;  // the caller refuses; nothing uploaded
+  if (!h->d_intr_meta) {
+    Dev& d = h->dev;
+    CHECK_RC(d.alloc(&h->d_intr_meta, (size_t)std::max(1, NI)));
+    CHECK_RC(d.alloc(&h->d_intr_act, (size_t)kIntrFreeMax));
+    CHECK_RC(d.alloc(&h->d_intr_c, (size_t)kIntr * std::max(1, NI)));
+    CHECK_RC(d.alloc(&h->d_zg, (size_t)kIntrFreeMax * kIntrRec));
+    CHECK_RC(d.alloc(&h->d_sz, (size_t)6 * kIntrFreeMax));
+    CHECK_RC(d.alloc(&h->d_dz, (size_t)6 * kIntrFreeMax));
+    CHECK_RC(d.alloc(&h->d_znorm, (size_t)16));
+    CHECK_RC(d.alloc(&h->d_zpart, (size_t)intr_eval_grid(h->view.N) * kIntrFreeMax * kIntrRec));
+    h->intr_meta.clear();
+  }
+  bool same = h->intr_meta.size() == meta.size();
+  for (size_t i = 0; same && i < meta.size(); ++i) same = meta[i].x == h->intr_meta[i].x && meta[i].y == h->intr_meta[i].y;
+  if (!same) {
+    HIP_OK(hipMemcpyAsync(h->d_intr_meta, meta.data(), sizeof(int2) * meta.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_OK(hipMemcpyAsync(h->d_intr_act, act, sizeof(act), hipMemcpyHostToDevice, h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));
+    h->intr_meta = meta;
+  }
+  h->nfi = nfi;
+  return 0;
+}
+// [U_zz | g_z | count] of the free intrinsics at the x on the handle (tables in d_camtab), all-reduced
+static int intr_eval(dab_handle* h) {
+  if (h->nfi <= 0) return 0;
+  launch_intr_eval(h->stream, h->view, h->d_points, h->d_camtab, h->d_intr_meta, h->nfi, h->d_zpart, h->d_zg);
+  return h->allreduce(h->d_zg, (size_t)h->nfi * kIntrRec, ncclSum);
+}
+
+extern "C" int dab_set_intrinsics_free(dab_handle* h, const uint8_t* groups) {
+  clear_error();
+  if (!h) return set_error(DAB_E_INVALID, "null handle");
+  if (!h->have_problem) return set_error(DAB_E_STATE, "no problem set");
+  if (groups)
+    for (int i = 0; i < h->NI; ++i)
+      if (groups[i] > 7) return set_error(DAB_E_INVALID, "intrinsic group bits above 7");
+  for (int i = 0; i < h->NI; ++i) h->intr_mask[(size_t)i] = groups ? groups[i] : 0;
+  return 0;
+}
+extern "C" int dab_get_intrinsics_free(dab_handle* h, uint8_t* groups, int32_t* num_free_intr,
+                                       int32_t* num_free_scalars) {
+  clear_error();
+  if (!h) return set_error(DAB_E_INVALID, "null handle");
+  if (!h->have_problem) return set_error(DAB_E_STATE, "no problem set");
+  if (groups)
+    for (int i = 0; i < h->NI; ++i) groups[i] = h->intr_mask[(size_t)i];
+  if (num_free_intr || num_free_scalars) {
+    int nfi = 0, nscal = 0;
+    if (!intr_mask_any(h)) {
+      // nothing requested (or freeze_camera): empty, no device use
+    } else if (!h->coll() || h->intr_ref_union) {
+      // the referenced set is known on the host: count there, the device and h->nfi untouched
+      for (int i = 0; i < h->NI; ++i) {
+        if (!h->intr_ref[(size_t)i]) continue;
+        const int ab = intr_struct_bits(h, i) & intr_group_bits(h->intr_mask[(size_t)i]);
+        nfi += ab != 0;
+        nscal += __builtin_popcount((unsigned)ab);
+      }
+    } else {
+      // several ranks, the referenced union not formed yet: the one collective of this call
+      HIP_OK(hipSetDevice(h->device));
+      CHECK_RC(intr_free_set(h, true, &nfi, &nscal));
+    }
+    if (num_free_intr) *num_free_intr = nfi;
+    if (num_free_scalars) *num_free_scalars = nscal;
+  }
+  return 0;
+}
+extern "C" int dab_get_intrinsics(dab_handle* h, double* intr) {
+  clear_error();
+  if (!h) return set_error(DAB_E_INVALID, "null handle");
+  if (!h->have_problem) return set_error(DAB_E_STATE, "no problem set");
+  if (!intr) return set_error(DAB_E_INVALID, "null intrinsics array");
+  HIP_OK(hipSetDevice(h->device));
+  std::vector<double> K((size_t)kIntr * std::max(1, h->NI));
+  HIP_OK(hipMemcpyAsync(K.data(), h->d_intr, sizeof(double) * K.size(), hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  for (int i = 0; i < h->NI; ++i) {
+    const int sb = intr_struct_bits(h, i);
+    for (int k = 0; k < 6; ++k)
+      intr[6 * (size_t)i + k] = ((sb >> k) & 1) ? K[(size_t)kIntr * i + k] : h->intr_host[6 * (size_t)i + k];
+  }
+  return 0;
+}
+extern "C" int dab_update_intrinsics(dab_handle* h, const double* intr) {
+  clear_error();
+  if (!h) return set_error(DAB_E_INVALID, "null handle");
+  if (!h->have_problem) return set_error(DAB_E_STATE, "no problem set");
+  if (!intr) return set_error(DAB_E_INVALID, "null intrinsics array");
+  HIP_OK(hipSetDevice(h->device));
+  std::vector<double> K((size_t)kIntr * std::max(1, h->NI), 0.0);
+  for (int i = 0; i < h->NI; ++i) {  // the device layout of set_problem: cx cy fx fy k0 k1 0 0
+    const double* in = intr + 6 * (size_t)i;
+    double* o = &K[(size_t)kIntr * i];
+    o[0] = in[0];
+    o[1] = in[1];
+    o[2] = in[2];
+    o[3] = h->intr_nf[i] == 2 ? in[3] : in[2];
+    o[4] = h->intr_nk[i] >= 1 ? in[4] : 0.0;
+    o[5] = h->intr_nk[i] >= 2 ? in[5] : 0.0;
+  }
+  HIP_OK(hipMemcpyAsync(h->d_intr, K.data(), sizeof(double) * K.size(), hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  h->intr_host.assign(intr, intr + 6 * (size_t)h->NI);
+  return 0;
+}
+extern "C" int dab_eval_intrinsic_jacobians(dab_handle* h, double* J) {
+  clear_error();
+  if (!h) return set_error(DAB_E_INVALID, "null handle");
+  if (!h->have_problem) return set_error(DAB_E_STATE, "no problem set");
+  if (!J) return set_error(DAB_E_INVALID, "null Jacobian array");
+  HIP_OK(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  // the kernel reads only which scalars each model has: its own table, the handle's free set
+  // (mask, meta, nfi) is neither read nor touched, and no rank waits for another
+  std::vector<int2> meta((size_t)std::max(1, h->NI), make_int2(-1, 0));
+  for (int i = 0; i < h->NI; ++i) meta[(size_t)i].y = (intr_struct_bits(h, i) << 8) | (h->intr_nf[i] == 1 ? 1 << 16 : 0);
+  int2* d_meta = nullptr;
+  double* d_J = nullptr;
+  CHECK_RC(h->dev.alloc(&d_meta, meta.size()));
+  CHECK_RC(h->dev.alloc(&d_J, (size_t)12 * std::max(1, h->NS)));
+  HIP_OK(hipMemcpyAsync(d_meta, meta.data(), sizeof(int2) * meta.size(), hipMemcpyHostToDevice, s));
+  launch_cam_tables(s, h->E, h->d_ext, h->d_camtab);
+  launch_intr_jac(s, h->view, h->d_points, h->d_camtab, d_meta, d_J);
+  std::vector<double> Jh((size_t)12 * h->NS);
+  HIP_OK(hipMemcpyAsync(Jh.data(), d_J, Jh.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  h->dev.drop(d_J);
+  h->dev.drop(d_meta);
+  for (int s2 = 0; s2 < h->NS; ++s2) {
+    const int o = h->perm[s2];
+    if (o < 0) continue;
+    std::memcpy(J + 12 * (size_t)o, Jh.data() + 12 * (size_t)s2, 12 * sizeof(double));
+  }
+  return 0;
+}
+extern "C" int dab_get_intrinsic_blocks(dab_handle* h, int32_t* num_free_intr, double* zg) {
+  clear_error();
+  if (!h) return set_error(DAB_E_INVALID, "null handle");
+  if (!h->have_problem) return set_error(DAB_E_STATE, "no problem set");
+  HIP_OK(hipSetDevice(h->device));
+  int nfi = 0;
+  CHECK_RC(intr_free_set(h, true, &nfi));
+  if (nfi > kIntrFreeMax) return set_error(DAB_E_UNSUPPORTED, "more than 16 free intrinsics");
+  if (num_free_intr) *num_free_intr = nfi;
+  if (zg && nfi > 0) {
+    std::vector<double> z((size_t)nfi * kIntrRec);
+    HIP_OK(hipMemcpyAsync(z.data(), h->d_zg, z.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < nfi; ++i) std::memcpy(zg + 27 * (size_t)i, z.data() + (size_t)kIntrRec * i, 27 * sizeof(double));
+  }
+  return 0;
+}
+
 extern "C" int dab_set_problem(dab_handle* h, const dab_problem* p) {
   const int rc = set_problem_impl(h, p);
   CHECK_RC(guard_fail(h, "dab_set_problem"));
@@ -2065,7 +2319,8 @@ static int set_problem_impl(dab_handle* h, const dab_problem* p) {
   const bool on_device = h->knobs.setup_host == 0 && setup_device_fits(h, p);
   if (on_device) CHECK_RC(setup_device(h, p, phase));
   else CHECK_RC(setup_host(h, p, phase));
-  return setup_buffers(h, phase);
+  CHECK_RC(setup_buffers(h, phase));
+  return intr_setup(h, p);
 }
 
 
@@ -3138,13 +3393,54 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
   const bool use_pcg = opt.linear_solver_type == DAB_LINEAR_SOLVER_IMPLICIT_SCHUR_PCG;
   HIP_OK(hipSetDevice(h->device));
   static const bool timing = getenv("DAB_SETUP_TIMING") != nullptr;
+  // free intrinsics: the refusals come first, so a refused solve leaves the handle as it was
+  int nfi = 0, nz_scal = 0;
+  if (intr_mask_any(h)) {
+    CHECK_RC(intr_free_set(h, true, &nfi, &nz_scal));
+    if (nfi > 0 && use_pcg)
+      return set_error(DAB_E_UNSUPPORTED, "free intrinsics need the exact step (DAB_LINEAR_SOLVER_EXPLICIT_SCHUR)");
+    if (nfi > kIntrFreeMax) return set_error(DAB_E_UNSUPPORTED, "more than 16 free intrinsics");
+    if (nfi > 0 && h->NC == 0) return set_error(DAB_E_UNSUPPORTED, "free intrinsics need a free extrinsic");
+  }
   const double tp0 = now_s();
   CHECK_RC(use_pcg ? build_pcg_buffers(h) : build_schur_tables(h));
   const double tp1 = now_s();
+  // the system with the block z: its own dense buffer of n' = 6 NC + 6 nfi rows (+ rhs row)
+  const int n2 = 6 * h->NC + 6 * nfi;
+  if (nfi > 0) {
+    h->ldz = ((n2 + 1 + 7) / 8) * 8;
+    if (h->ldz % 512 == 0) h->ldz += 8;
+    const size_t need = (size_t)(n2 + 1) * h->ldz;
+    if (need > h->Sz_cap) {
+      h->dev.drop(h->d_Sz);
+      h->d_Sz = nullptr;
+      h->Sz_cap = 0;
+      CHECK_RC(h->dev.alloc(&h->d_Sz, need));
+      h->Sz_cap = need;
+    }
+    if (!h->d_yz) {
+      CHECK_RC(h->dev.alloc(&h->d_yz, (size_t)6 * h->NC + 6 * kIntrFreeMax));
+      CHECK_RC(h->dev.alloc(&h->d_bsum, (size_t)6 * kIntrFreeMax * (6 * (size_t)h->NC + 6 * kIntrFreeMax + 1)));
+      CHECK_RC(h->dev.alloc(&h->d_ptmask, (size_t)std::max(1, h->NP)));
+    }
+    launch_intr_ptmask(h->stream, h->view, h->d_intr_meta, h->d_ptmask);
+    int spg = 1;
+    const size_t bneed = (size_t)intr_border_groups(h->view.nslice, h->NC, nfi, &spg) * (size_t)(6 * nfi) * (n2 + 1);
+    if (bneed > h->bpart_cap) {
+      h->dev.drop(h->d_bpart);
+      h->d_bpart = nullptr;
+      h->bpart_cap = 0;
+      CHECK_RC(h->dev.alloc(&h->d_bpart, bneed));
+      h->bpart_cap = bneed;
+    }
+  }
+  double* const S_ = nfi > 0 ? h->d_Sz : h->d_S;
+  const int ld_ = nfi > 0 ? h->ldz : h->lds;
+  double* const yc_ = nfi > 0 ? h->d_yz : h->d_yc;
   // the dense factorisation's scratch and captured graph belong to the set-up, not to the
   // first LM iteration (kept while the camera count and the buffers stay the same)
   if (!use_pcg && h->NC > 0 &&
-      chol_prepare(h->chol, h->stream, 6 * h->NC, h->d_S, h->lds, h->d_yc, h->d_flags + 1) != 0)
+      chol_prepare(h->chol, h->stream, n2, S_, ld_, yc_, h->d_flags + 1) != 0)
     return set_error(DAB_E_DEVICE, "dense Cholesky set-up failed");
   if (timing)
     std::fprintf(stderr, "solve prep: %s %.2f ms, Cholesky graph %.2f ms\n", use_pcg ? "pcg buffers" : "schur tables",
@@ -3169,7 +3465,7 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
   sum->num_successful_steps = sum->num_unsuccessful_steps = 0;
   sum->num_iterations = 0;
   sum->num_residuals = 2 * h->N;
-  sum->num_parameters = 3 * NP + 6 * NC;
+  sum->num_parameters = 3 * NP + 6 * NC + nz_scal;
   sum->num_free_points = NP;
   sum->num_free_ext = NC;
   sum->jacobian_evaluation_time_in_seconds = 0;
@@ -3181,6 +3477,18 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
                                 : (h->schur_tiles ? DAB_SCHUR_TILES : DAB_SCHUR_PAIRS);
   const bool verbose = opt.minimizer_progress_to_stdout && h->rank == 0;
   const bool in_global = true;  (void)in_global;
+  // the rows of the block z: the rhs moves to row n', then the border sums (one point-major pass,
+  // whichever assembly built the leading n x n part), all-reduced and scattered into S
+  auto intr_border = [&](const StepScalars& sc) -> int {
+    if (nfi <= 0) return 0;
+    HIP_OK(hipMemcpyAsync(S_ + (size_t)n2 * ld_, S_ + (size_t)n * ld_, sizeof(double) * (size_t)n,
+                          hipMemcpyDeviceToDevice, s));
+    launch_intr_border(s, v, h->d_points, h->d_camtab, h->d_scale_c, h->d_L, h->d_q, h->d_sz, h->d_intr_meta,
+                       h->d_ptmask, nfi, h->d_bpart, h->d_bsum, h->knobs.intr_border_lds != 0);
+    CHECK_RC(h->allreduce(h->d_bsum, (size_t)(6 * nfi) * (size_t)(n2 + 1), ncclSum));
+    launch_intr_scatter(s, n, nfi, h->d_bsum, h->d_zg, h->d_sz, h->d_intr_act, sc, S_, ld_);
+    return 0;
+  };
 
   // ---- iteration 0 ----
   // a solve starts with a clean sticky error word (a timed-out wait of an earlier call was
@@ -3188,18 +3496,41 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
   HIP_OK(hipMemsetAsync(h->d_scal + S_XERR, 0, sizeof(double), s));
   double t0 = now_s();
   CHECK_RC(eval_jacobian_and_blocks(h, true));
+  // intrinsic sums and norms at x (k_intr_eval after every evaluation pass); hz = their host copy:
+  // [0..4] of the candidate, [8..12] at x, as launch_cam_norms orders them
+  double hz[16] = {0};
+  auto intr_at_x = [&]() -> int {
+    if (nfi <= 0) return 0;
+    CHECK_RC(intr_eval(h));
+    launch_intr_candidate(s, h->NI, h->d_intr_meta, h->d_intr, h->d_sz, nullptr, h->d_zg, nullptr, nullptr,
+                          h->d_znorm + 8);
+    return 0;
+  };
+  auto read_znorm = [&]() -> int {
+    if (nfi <= 0) return 0;
+    HIP_OK(hipMemcpyAsync(hz, h->d_znorm, sizeof(hz), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    return 0;
+  };
+  CHECK_RC(intr_at_x());
+  CHECK_RC(read_znorm());
   CHECK_RC(read_scalars(h));
   if (timing) std::fprintf(stderr, "solve iteration 0: %.2f ms\n", 1e3 * (now_s() - t0));
   {
     const int g3 = grid_for(3 * NP, 256, 1 << 20);
     k_scale_points<<<g3, 256, 0, s>>>(NP, h->d_V, h->d_scale_p, opt.jacobi_scaling);
     if (NC > 0) k_scale_cams<<<grid_for(6 * NC, 256, 1 << 20), 256, 0, s>>>(NC, h->ug(), h->d_scale_c, opt.jacobi_scaling);
+    launch_intr_scale(s, nfi, h->d_zg, h->d_intr_act, h->d_sz, opt.jacobi_scaling);
   }
   sum->jacobian_evaluation_time_in_seconds += now_s() - t0;
   double x_cost = 0.5 * h->h_scal[S_COST];
   bool eval_ok = h->h_scal[S_COST_BAD] == 0.0;
   double gmax = std::max(h->h_scal[S_GMAX_P], h->h_scal[S_CAM0 + 2]);
   double x_norm = std::sqrt(h->h_scal[S_XNORM_P] + h->h_scal[S_CAM0 + 4]);
+  if (nfi > 0) {
+    gmax = std::max(gmax, hz[8 + 2]);
+    x_norm = std::sqrt(h->h_scal[S_XNORM_P] + h->h_scal[S_CAM0 + 4] + hz[8 + 4]);
+  }
   sum->initial_cost = x_cost;
   double final_cost = x_cost;
   if (!eval_ok) {
@@ -3299,10 +3630,11 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
       launch_schur_sum_tiles(s, a, h->d_sblk);
       CHECK_RC(h->allreduce(h->d_sblk, (size_t)a.nelem, ncclSum));
       CHECK_RC(h->allreduce_u64(reinterpret_cast<uint64_t*>(h->d_rfx), (size_t)6 * NC));
-      HIP_OK(hipMemsetAsync(h->d_S, 0, sizeof(double) * (size_t)(n + 1) * h->lds, s));
-      launch_schur_unpack(s, NC, h->d_sblk, h->d_rfx, h->d_kx, a.kq, h->d_S, h->lds, h->ybc());
-      launch_s_add_u(s, NC, h->ug(), h->ncross, h->d_cross_cam, h->Ux(), h->d_scale_c, sc, h->ybc(), h->d_S, h->lds);
-      if (chol_factor_solve(h->chol, s, n, h->d_S, h->lds, h->d_yc, h->d_flags + 1) != 0)
+      HIP_OK(hipMemsetAsync(S_, 0, sizeof(double) * (size_t)(n + 1) * ld_, s));
+      launch_schur_unpack(s, NC, h->d_sblk, h->d_rfx, h->d_kx, a.kq, S_, ld_, h->ybc());
+      launch_s_add_u(s, NC, h->ug(), h->ncross, h->d_cross_cam, h->Ux(), h->d_scale_c, sc, h->ybc(), S_, ld_);
+      CHECK_RC(intr_border(sc));
+      if (chol_factor_solve(h->chol, s, n2, S_, ld_, yc_, h->d_flags + 1) != 0)
         return set_error(DAB_E_DEVICE, "dense Cholesky launch failed");
     } else if (NC > 0) {
       // fp64 Y: the camera-major pass writes the [NE][18] records the S blocks gather (no
@@ -3313,36 +3645,48 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
       // fill of the whole matrix and no scatter; several: packed, all-reduced, unpacked
       const bool direct = h->world == 1;
       launch_s_blocks(s, h->nblk, h->d_blk_pair_beg, h->d_pairs, rec ? nullptr : h->d_Y, h->NE, h->packed(),
-                      h->d_Yrec, direct ? h->d_S : nullptr, h->lds, h->d_blk_cam, h->nzero, h->d_blk_zero);
+                      h->d_Yrec, direct ? S_ : nullptr, ld_, h->d_blk_cam, h->nzero, h->d_blk_zero);
       launch_cam_rhs_partial(s, v, h->nchunk, h->d_chunk_beg, rec ? h->d_Yrec : h->d_Y, h->d_q, h->d_partial, rec);
       launch_seg_final(s, NC, 6, h->d_seg_chunk, h->d_partial, h->ybc(), h->max_seg_chunks);
       if (direct) {
-        launch_s_add_u(s, NC, h->ug(), h->ncross, h->d_cross_cam, h->Ux(), h->d_scale_c, sc, h->ybc(), h->d_S,
-                       h->lds);
+        launch_s_add_u(s, NC, h->ug(), h->ncross, h->d_cross_cam, h->Ux(), h->d_scale_c, sc, h->ybc(), S_, ld_);
       } else {
         CHECK_RC(h->allreduce(h->d_spack, h->spack_count(), ncclSum));
         launch_s_unpack(s, NC, h->nblk, h->d_blk_cam, h->packed(), h->ug(), h->ncross, h->d_cross_cam, h->Ux(),
-                        h->d_scale_c, sc, h->ybc(), h->d_S, h->lds);
+                        h->d_scale_c, sc, h->ybc(), S_, ld_);
       }
-      if (chol_factor_solve(h->chol, s, n, h->d_S, h->lds, h->d_yc, h->d_flags + 1) != 0)
+      CHECK_RC(intr_border(sc));
+      if (chol_factor_solve(h->chol, s, n2, S_, ld_, yc_, h->d_flags + 1) != 0)
         return set_error(DAB_E_DEVICE, "dense Cholesky launch failed");
     }
     if ((use_pcg && h->mf) || (!use_pcg && h->schur_tiles))
-      launch_mf_backsub(s, v, h->d_points, h->d_camtab, h->d_scale_c, h->d_L, h->d_q, h->d_yc, h->d_dp, h->mf_grid_n);
+      launch_mf_backsub(s, v, h->d_points, h->d_camtab, h->d_scale_c, h->d_L, h->d_q, yc_, h->d_dp, h->mf_grid_n);
     else
-      launch_backsub(s, v, h->d_L, h->d_q, yb, NC > 0 ? h->d_yc : nullptr, h->d_dp);
+      launch_backsub(s, v, h->d_L, h->d_q, yb, NC > 0 ? yc_ : nullptr, h->d_dp);
+    // the y_z term of the point step, whichever back substitution ran
+    if (nfi > 0)
+      launch_intr_backsub(s, v, h->d_points, h->d_camtab, h->d_L, h->d_sz, yc_ + n, h->d_intr_meta, h->d_dp);
     // candidate x + delta and the model / candidate cost in one observation pass
     launch_axpy_points(s, NP, h->d_points, h->d_dp, h->d_points_c, h->d_gpart, h->red_grid);
     launch_final_sum(s, h->red_grid, 2, h->d_gpart, h->d_scal + S_STEP_P);
-    launch_cam_candidate(s, h->E, h->d_ext_col, h->d_ext, NC > 0 ? h->d_yc : nullptr, h->d_scale_c, h->d_ext_c,
+    launch_cam_candidate(s, h->E, h->d_ext_col, h->d_ext, NC > 0 ? yc_ : nullptr, h->d_scale_c, h->d_ext_c,
                          h->d_dc);
     launch_cam_norms(s, h->E, h->d_ext_col, h->d_ext, h->d_ext_c, nullptr, h->d_scal + S_CAM0);
     launch_cam_tables(s, h->E, h->d_ext_c, h->d_camtab_c);
     const double tre = now_s();
-    launch_candidate(s, v, h->d_points, h->d_camtab, h->d_dp, h->d_dc, h->d_camtab_c, h->d_gpart, h->red_grid);
+    if (nfi > 0) {
+      // candidate intrinsics, delta_z and their norms; the candidate pass with the z term
+      launch_intr_candidate(s, h->NI, h->d_intr_meta, h->d_intr, h->d_sz, yc_ + n, nullptr, h->d_intr_c, h->d_dz,
+                            h->d_znorm);
+      launch_candidate_z(s, v, h->d_points, h->d_camtab, h->d_dp, h->d_dc, h->d_camtab_c, h->d_intr_meta, h->d_dz,
+                         h->d_intr_c, h->d_gpart, h->red_grid);
+    } else {
+      launch_candidate(s, v, h->d_points, h->d_camtab, h->d_dp, h->d_dc, h->d_camtab_c, h->d_gpart, h->red_grid);
+    }
     launch_final_sum(s, h->red_grid, 3, h->d_gpart, h->d_scal + S_MODEL);
     CHECK_RC(h->allreduce(h->d_scal + S_MODEL, 5, ncclSum));
     CHECK_RC(h->allreduce_max_i32(h->d_flags, 4));
+    CHECK_RC(read_znorm());
     CHECK_RC(read_scalars(h));
     // bit 2 of the Cholesky flag: a bounded wait inside the factorisation gave up (a
     // scheduling / residency fault, not a property of the matrix): an error, not a
@@ -3376,7 +3720,8 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
     num_invalid = 0;
     const double candidate_cost = h->h_scal[S_CAND_BAD] != 0.0 ? 1.7976931348623157e308 : 0.5 * h->h_scal[S_CAND];
     // ParameterToleranceReached
-    it.step_norm = std::sqrt(h->h_scal[S_STEP_P] + h->h_scal[S_CAM0 + 0]);
+    it.step_norm = nfi > 0 ? std::sqrt(h->h_scal[S_STEP_P] + h->h_scal[S_CAM0 + 0] + hz[0])
+                           : std::sqrt(h->h_scal[S_STEP_P] + h->h_scal[S_CAM0 + 0]);
     if (it.step_norm <= opt.parameter_tolerance * (x_norm + opt.parameter_tolerance)) {
       term = DAB_CONVERGENCE;
       std::snprintf(sum->message, sizeof(sum->message), "Parameter tolerance reached. Relative step_norm: %e <= %e.",
@@ -3394,13 +3739,20 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
     it.relative_decrease = (x_cost - candidate_cost) / model_cost_change;
     if (it.relative_decrease > opt.min_relative_decrease) {
       // HandleSuccessfulStep: x <- candidate, re-evaluate J at the new point
-      const double xc_norm = std::sqrt(h->h_scal[S_XCNORM_P] + h->h_scal[S_CAM0 + 1]);
+      const double xc_norm = nfi > 0 ? std::sqrt(h->h_scal[S_XCNORM_P] + h->h_scal[S_CAM0 + 1] + hz[1])
+                                     : std::sqrt(h->h_scal[S_XCNORM_P] + h->h_scal[S_CAM0 + 1]);
       std::swap(h->d_points, h->d_points_c);
       std::swap(h->d_ext, h->d_ext_c);
       std::swap(h->d_camtab, h->d_camtab_c);  // the candidate pass built the tables of x + delta
+      if (nfi > 0) {  // every kernel reads the intrinsics through the view
+        std::swap(h->d_intr, h->d_intr_c);
+        h->view.intr = h->d_intr;
+      }
       x_norm = xc_norm;
       const double tj = now_s();
       CHECK_RC(eval_jacobian_and_blocks(h, true, true));
+      CHECK_RC(intr_at_x());
+      CHECK_RC(read_znorm());
       CHECK_RC(read_scalars(h));
       sum->jacobian_evaluation_time_in_seconds += now_s() - tj;
       if (h->h_scal[S_COST_BAD] != 0.0) {
@@ -3410,6 +3762,7 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
       }
       x_cost = 0.5 * h->h_scal[S_COST];
       gmax = std::max(h->h_scal[S_GMAX_P], h->h_scal[S_CAM0 + 2]);
+      if (nfi > 0) gmax = std::max(gmax, hz[8 + 2]);
       it.step_is_successful = 1;
       it.cost = x_cost;
       it.gradient_max_norm = gmax;
@@ -3447,6 +3800,13 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
 // The LM kernels run unchanged with radius = +inf: their sqrt(clamp(d) / radius) is exactly 0.
 static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, double* point_cov, double* ext_cov,
                            double* ext_full, dab_covariance_info* info) {
+  if (h && h->have_problem && intr_mask_any(h)) {
+    // free intrinsics are not part of the covariance: it would report them as exactly known
+    int nfi_cov = 0;
+    HIP_OK(hipSetDevice(h->device));
+    CHECK_RC(intr_free_set(h, true, &nfi_cov));
+    if (nfi_cov > 0) return set_error(DAB_E_UNSUPPORTED, "dab_covariance with free intrinsics is not supported");
+  }
   clear_error();
   if (!h) return set_error(DAB_E_INVALID, "null handle");
   dab_covariance_options opt;
@@ -3823,6 +4183,15 @@ extern "C" int dab_bench_eval_pass(dab_handle* h, int with_assembly, int count) 
   // even fence-free, four event records add ~10 us to a ~40 us pass, so timing every pass
   // would distort the throughput it measures. DAB_BENCH_SAMPLE overrides (0 = no events).
   const int sample = h->knobs.bench_sample;
+  // a non-empty free set: the intrinsic sums of each pass too (dab_get_intrinsic_blocks)
+  int bench_nfi = 0;
+  if (intr_mask_any(h)) CHECK_RC(intr_free_set(h, true, &bench_nfi));
+  if (bench_nfi > kIntrFreeMax) return set_error(DAB_E_UNSUPPORTED, "more than 16 free intrinsics");
+  auto intr_pass = [&]() -> int {
+    if (bench_nfi <= 0) return 0;
+    launch_cam_tables(s, h->E, h->d_ext, h->d_camtab);
+    return intr_eval(h);
+  };
   for (int step = 0; step < count; ++step) {
     // every bench pass is an evaluation at a NEW linearization point, as in the LM loop
     // after an accepted step (sfm.cc:66-73, Ceres re-linearises each iteration): the pass
@@ -3831,6 +4200,7 @@ extern "C" int dab_bench_eval_pass(dab_handle* h, int with_assembly, int count) 
     if (sample <= 0 || step % sample != 0) {
       CHECK_RC(eval_pass(h, false));
       CHECK_RC(h->allreduce_cost());
+      CHECK_RC(intr_pass());
       continue;
     }
     // per-step events from a pool: nothing here waits for the device, so back-to-back
@@ -3854,6 +4224,7 @@ extern "C" int dab_bench_eval_pass(dab_handle* h, int with_assembly, int count) 
       CHECK_RC(eval_pass(h, false, ev[1], ev[2], ev[4], ev[5], &prec));
       h->bench_pair_rec[slot] = prec;
       CHECK_RC(h->allreduce_cost());
+      CHECK_RC(intr_pass());
     } else {
       if (eval_points_needs_camtab(h->eval_wps)) launch_cam_tables(s, h->E, h->d_ext, h->d_camtab);
       HIP_OK(hipEventRecord(ev[1], s));

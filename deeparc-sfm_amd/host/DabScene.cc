@@ -67,6 +67,12 @@ void DabScene::build(DeepArcManager& m, bool freeze_camera) {
       ext[6 * i + k] = exts[i]->rotation()[k];
       ext[6 * i + 3 + k] = exts[i]->translation()[k];
     }
+  refresh_intrinsics(m);
+  bind(freeze_camera);
+}
+
+void DabScene::refresh_intrinsics(DeepArcManager& m) {
+  std::vector<Intrinsic*>& ks = *m.intrinsics();
   intr.assign(6 * ks.size(), 0.0);
   intr_nf.resize(ks.size());
   intr_nk.resize(ks.size());
@@ -82,7 +88,20 @@ void DabScene::build(DeepArcManager& m, bool freeze_camera) {
     o[4] = intr_nk[i] >= 1 ? k->distrotion()[0] : 0.0;
     o[5] = intr_nk[i] >= 2 ? k->distrotion()[1] : 0.0;
   }
-  bind(freeze_camera);
+}
+
+void DabScene::write_back_intrinsics(DeepArcManager& m) {
+  std::vector<Intrinsic*>& ks = *m.intrinsics();
+  for (size_t i = 0; i < ks.size() && 6 * i + 5 < intr.size(); ++i) {
+    Intrinsic* k = ks[i];
+    const double* o = &intr[6 * i];
+    k->center()[0] = o[0];
+    k->center()[1] = o[1];
+    k->focal()[0] = o[2];
+    if (k->focal_size() == 2) k->focal()[1] = o[3];
+    if (k->distrotion_size() >= 1) k->distrotion()[0] = o[4];
+    if (k->distrotion_size() >= 2) k->distrotion()[1] = o[5];
+  }
 }
 
 void DabScene::bind(bool freeze_camera) {

@@ -25,6 +25,10 @@ struct DabScene {
   void write_back(DeepArcManager& m);
   // the manager's current parameter values into points / ext (same structure as build)
   void refresh_values(DeepArcManager& m);
+  // intrinsics: the manager's values into intr (dab_problem layout), and intr back into the
+  // manager's Intrinsic objects (the scalars each model has)
+  void refresh_intrinsics(DeepArcManager& m);
+  void write_back_intrinsics(DeepArcManager& m);
   // the arrays of the manager after filterPoint3d dropped the blocks with keep_obs[o] == 0 and
   // the points with keep_pt[i] == 0 (survivors in order, as the manager compacts its lists):
   // the same arrays build() would make, without walking the blocks

@@ -57,6 +57,13 @@ class DeepArcManager {
   }
   int lossType() const { return loss_type_; }
   double lossScale() const { return loss_scale_; }
+  // Intrinsic groups every solve() of this manager refines (DAB_INTR_* bits of dab.h, one value
+  // for every intrinsic): the equivalent of deleting sfm.cc:60-62. Kept across the pipeline's
+  // re-set-ups beside the loss and applied after every dab_set_problem. The refined doubles go
+  // back into the Intrinsic objects untruncated (Ceres writes through ParameterBlock::get()'s
+  // pointers; quirk Q1's truncation is the reader's), so write() and the accessors see them.
+  void setIntrinsicsFree(int groups) { intr_free_ = groups; }
+  int intrinsicsFree() const { return intr_free_; }
 
   // Covariance of the current scene at its current parameters (dab_covariance in dab.h: Sigma =
   // (J^T J)^-1 under this manager's loss, no sigma^2 factor; ceres::Covariance). The reference's
@@ -85,6 +92,7 @@ class DeepArcManager {
   unsigned long long structure_version_ = 0;
   int loss_type_ = 0;  // DAB_LOSS_TRIVIAL
   double loss_scale_ = 1.0;
+  int intr_free_ = 0;  // all constant (sfm.cc:60-62)
   int arc_size_ = 0, ring_size_ = 0;
   bool share_extrinsic_ = false;
   std::map<int, std::map<int, Camera*> > hemisphere_;

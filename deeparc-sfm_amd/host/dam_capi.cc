@@ -143,6 +143,14 @@ int dam_set_loss(dam_manager* m, int32_t loss_type, double scale) {
   });
 }
 
+int dam_set_intrinsics_free(dam_manager* m, int32_t groups) {
+  return guarded([&] {
+    if (!m) throw "null manager";
+    if (groups < 0 || groups > 7) throw "intrinsic group bits above 7";
+    m->m.setIntrinsicsFree(groups);
+  });
+}
+
 int dam_covariance(dam_manager* m, const int32_t* extra_const, int32_t n_extra, int32_t freeze_camera,
                    double* point_cov, double* ext_cov, double* ext_full, int32_t* ext_label,
                    dab_covariance_info* info) {

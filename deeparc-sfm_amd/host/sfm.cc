@@ -22,9 +22,22 @@ int solveWith(DeepArcManager& m, const dab_options& options, bool freeze_camera,
   dab_summary* s = summary ? summary : &local;
   rc = dab_set_loss(dh.h, m.lossType(), m.lossScale());  // sfm.cc:48: the residual blocks' loss
   if (rc) return rc;
+  // sfm.cc:60-62 deleted for the manager's groups: the mask after every (re-)set-up, and the
+  // manager's current intrinsic values on the handle (a resident problem keeps refined ones)
+  const bool free_intr = m.intrinsicsFree() != 0;
+  if (free_intr) {
+    const std::vector<uint8_t> groups(scene.intr_nf.size(), (uint8_t)m.intrinsicsFree());
+    scene.refresh_intrinsics(m);
+    rc = dab_update_intrinsics(dh.h, scene.intr.data());
+    if (!rc) rc = dab_set_intrinsics_free(dh.h, groups.data());
+  } else {
+    rc = dab_set_intrinsics_free(dh.h, nullptr);
+  }
+  if (rc) return rc;
   const double t0 = dab_now_seconds();
   rc = dab_solve(dh.h, &options, s);
-  if (rc == DAB_E_UNSUPPORTED && options.linear_solver_type == DAB_LINEAR_SOLVER_EXPLICIT_SCHUR) {
+  // (not with free intrinsics: they need the exact step, and PCG's refusal would hide the reason)
+  if (rc == DAB_E_UNSUPPORTED && options.linear_solver_type == DAB_LINEAR_SOLVER_EXPLICIT_SCHUR && !free_intr) {
     // The explicit reduced system is refused only when it is both too large for the LDS
     // tiles (more than 160 free cameras) and too large for the pair tables (> 2e8 entry
     // pairs). The step is then the inexact implicit-Schur PCG one: say so, and the summary
@@ -43,6 +56,11 @@ int solveWith(DeepArcManager& m, const dab_options& options, bool freeze_camera,
   S.t.lm += s->total_time_in_seconds;
   S.t.prep += (t1 - t0) - s->total_time_in_seconds;
   scene.write_back(m);  // dab_solve wrote the optimised values into scene.points / ext
+  if (free_intr) {      // the refined intrinsics stay on the handle: fetch them, untruncated
+    rc = dab_get_intrinsics(dh.h, scene.intr.data());
+    if (rc) return rc;
+    scene.write_back_intrinsics(m);
+  }
   S.t.writeback += dab_now_seconds() - t1;
   return 0;
 }

@@ -45,6 +45,7 @@ SIGNATURES = {
     "dam_solve": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                             C.POINTER(_abi.DabSummary)]),
     "dam_set_loss": (C.c_int, [C.c_void_p, C.c_int32, C.c_double]),
+    "dam_set_intrinsics_free": (C.c_int, [C.c_void_p, C.c_int32]),
     "dam_covariance": (C.c_int, [C.c_void_p, _ip, C.c_int32, C.c_int32, _dp, _dp, _dp, _ip,
                                  C.POINTER(_abi.DabCovarianceInfo)]),
     "dam_filter": (C.c_int, [C.c_void_p, C.c_double, _dp, C.c_double]),
@@ -145,6 +146,12 @@ class DeepArcManager:
         """Robust loss of every later solve() of this manager (dam_set_loss): kind as
         core.Solver.set_loss, e.g. set_loss("cauchy", 0.5) for `new ceres::CauchyLoss(0.5)`."""
         _check(self.lib.dam_set_loss(self.h, _abi.loss_kind(kind), float(scale)))
+
+    def set_intrinsics_free(self, groups):
+        """Intrinsic groups (DAB_INTR_* bits) every later solve() of this manager refines
+        (dam_set_intrinsics_free): the equivalent of deleting sfm.cc:60-62. cameras() and write()
+        see the refined values."""
+        _check(self.lib.dam_set_intrinsics_free(self.h, int(groups)))
 
     def covariance(self, extra_const=(), freeze_camera=False, full=False):
         """DeepArcManager::covariance (dam_covariance): the covariance of the current scene at its

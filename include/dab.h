@@ -61,7 +61,8 @@ extern "C" {
  * translation (the two 3-blocks of Extrinsic.hh:32).
  * Intrinsic layout: intr[i] = (cx, cy, f0, f1, k0, k1) with intr_nf[i] in {1,2},
  * intr_nk[i] in {0,1,2} (Intrinsic.hh:32; unused slots ignored).
- * Intrinsics are never optimised (sfm.cc:54-63).
+ * Intrinsics are constant by default, as in the reference (sfm.cc:54-63);
+ * dab_set_intrinsics_free frees them by group for the exact step.
  * Constancy: points are free; an extrinsic is free unless ext_const[e] != 0 or
  * freeze_camera != 0 (sfm.cc:50-57). Parameter blocks referenced by no observation
  * are not part of the problem (Ceres only knows blocks added via AddResidualBlock)
@@ -263,6 +264,62 @@ int dab_set_loss(dab_handle* h, int32_t loss_type, double scale);
 int dab_get_loss(dab_handle* h, int32_t* loss_type, double* scale);
 /* Copy the device-resident parameters into host arrays (either may be NULL). */
 int dab_get_parameters(dab_handle* h, double* points, double* ext);
+
+/* ---- free intrinsics (self-calibration) -------------------------------------------------
+ * ParameterBlock::get() hands Ceres the principal point, the focal length and the distortion
+ * as parameter blocks [1], [2], [3], and sfm.cc:60-62 freezes them with three
+ * SetParameterBlockConstant lines. Deleting those lines is, here, a mask on the handle: one
+ * byte of DAB_INTR_* group bits per intrinsic (NULL = all constant, the default).
+ *
+ * Free set. The mask is state of the handle, set after dab_set_problem; dab_set_problem resets
+ * it to all-constant (num_intr may change). It takes effect at the next dab_solve. An intrinsic
+ * is free when some observation on some rank references it and its groups select at least one
+ * active scalar: CENTER cx, cy; FOCAL f0 (and f1 when nf == 2; with nf == 1 the one focal
+ * length drives both fx and fy'); DISTORTION k0 .. k_{nk-1}. Unreferenced intrinsics stay
+ * untouched and uncounted, as unreferenced extrinsics do. dab_summary.num_parameters grows by
+ * the active scalars. In a multi-rank handle every rank sets the same mask; dab_solve,
+ * dab_covariance and dab_bench_eval_pass are collective, and so is the first
+ * dab_get_intrinsics_free with a count pointer and a non-empty mask (the referenced union is
+ * formed once per problem). On a single-rank handle dab_get_intrinsics_free counts on the host
+ * and touches neither the device nor the handle's state.
+ * With freeze_camera != 0 the mask is ignored: the handle takes the freeze path unchanged
+ * (sfm.cc:54-57 freezes every block but the point). With an empty free set every call gives
+ * bitwise what it gives on a handle whose mask was never set.
+ *
+ * Refined values stay on the handle: dab_problem.intr is const and is never written;
+ * dab_get_intrinsics returns them ([num_intr][6], dab_problem layout; slots the model does not
+ * have keep the problem's values), dab_update_intrinsics replaces them, and every later call
+ * on the handle (residuals, Jacobians, filter, benchmark hooks, covariance) uses them.
+ *
+ * The step: the exact Schur step with a block z of six slots per free intrinsic bordering the
+ * reduced camera system ("Free intrinsics"); Jacobi scaling, LM diagonal, loss
+ * scaling, step norms and tolerances extend over the active scalars with the cameras' formulas.
+ *
+ * dab_eval_intrinsic_jacobians: raw, unscaled d r / d (cx, cy, f0, f1, k0, k1) per observation
+ * in the caller's order, [num_obs][2][6] row-major, at the parameters on the handle; columns
+ * of scalars the intrinsic's model does not have are zero, and with nf == 1 the f0 column
+ * carries both rows. dab_get_intrinsic_blocks: per free intrinsic (ascending index) the sums of
+ * the last evaluation that formed them, U_zz upper-packed (21) | g_z (6), over the active
+ * columns, in dab_bench_get_blocks' convention (rows scaled by sqrt(rho') under a loss, summed
+ * over the ranks). dab_solve forms them at every evaluation, dab_bench_eval_pass (with
+ * assembly) when the free set is not empty. Query *num_free_intr with zg NULL first.
+ *
+ * Refusals, fail closed, state unchanged. dab_solve with a non-empty free set returns
+ * DAB_E_UNSUPPORTED for IMPLICIT_SCHUR_PCG (requested or chosen by AUTO), for more than 16 free
+ * intrinsics, and for a problem without a free extrinsic (unless freeze_camera is set);
+ * dab_covariance with a non-empty free set returns DAB_E_UNSUPPORTED (it would report the
+ * intrinsics as exactly known). DAB_E_INVALID for a null handle (checked before any device
+ * use), a null array where one is required, or group bits above 7; DAB_E_STATE before
+ * dab_set_problem. */
+#define DAB_INTR_CENTER     1   /* cx, cy                      block [1], sfm.cc:60 */
+#define DAB_INTR_FOCAL      2   /* f0, and f1 when nf == 2     block [2], sfm.cc:61 */
+#define DAB_INTR_DISTORTION 4   /* k0 .. k_{nk-1}              block [3], sfm.cc:62 */
+int dab_set_intrinsics_free(dab_handle* h, const uint8_t* groups /* [num_intr], NULL = all constant */);
+int dab_get_intrinsics_free(dab_handle* h, uint8_t* groups, int32_t* num_free_intr, int32_t* num_free_scalars);
+int dab_get_intrinsics(dab_handle* h, double* intr /* [num_intr][6], dab_problem layout */);
+int dab_update_intrinsics(dab_handle* h, const double* intr);
+int dab_eval_intrinsic_jacobians(dab_handle* h, double* J /* [num_obs][2][6], caller order */);
+int dab_get_intrinsic_blocks(dab_handle* h, int32_t* num_free_intr, double* zg /* [nfi][27] = U_zz upper 21 | g_z 6 */);
 
 /* ---- evaluation (parity / filterPoint3d) ---------------------------------------------
  * residuals: [num_obs][2] in the caller's observation order.

@@ -53,6 +53,12 @@ int dam_solve(dam_manager* m, int32_t max_iteration, int32_t max_second, int32_t
  * manager; the default is the reference's NULL loss (sfm.cc:48-49). A bad type or scale
  * returns an error and leaves the loss as it was. dam_filter keeps the bare residual. */
 int dam_set_loss(dam_manager* m, int32_t loss_type, double scale);
+/* Intrinsic groups (DAB_INTR_* bits of dab.h, for every intrinsic) that every later solve of
+ * this manager refines: the equivalent of deleting sfm.cc:60-62. The default 0 keeps them
+ * constant as the reference does. The refined values are written back into the manager's
+ * intrinsics untruncated, so dam_get_cameras and dam_write see them. Bits above 7 return an
+ * error and leave the setting as it was. */
+int dam_set_intrinsics_free(dam_manager* m, int32_t groups);
 /* DeepArcManager::covariance: dab_covariance (dab.h) of the manager's current scene at its
  * current parameters, under the manager's loss. extra_const[n_extra]: extrinsic indices held
  * constant beside the gauge rule's; the reference's rule leaves the rig's global scale free

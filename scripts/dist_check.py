@@ -8,6 +8,11 @@ Schur and PCG). With --device D every rank uses device D (ranks sharing one GPU;
 refuses that, so pair it with --host-collective, which stages the library's collectives
 through gloo and exercises every other part of the sharded path). --loss kind:scale sets a
 robust loss (dab_set_loss) on every rank's handle and on the single handle it is compared with.
+--free-intrinsics G sets the DAB_INTR_* groups G free on every intrinsic (dab_set_intrinsics_free),
+on every rank's handle and on the single handle; the refined intrinsics are compared too (the exact
+step only: pair it with --solvers explicit).
+--expect-auto-refused checks instead that LINEAR_SOLVER_AUTO, where it picks PCG (several ranks, a
+camera system that is not a small one), refuses a non-empty free set on every rank.
 --covariance checks dab_covariance instead: every rank calls it on its shard after the solve, and
 rank 0 compares the camera arrays across the ranks (bitwise) and, with every owner's point rows,
 against a single handle at the same parameters.
@@ -52,6 +57,13 @@ def main():
                     "(DAB_EVAL_SIDE=7): every rank's dab_solve must fail with the timeout, none may hang")
     ap.add_argument("--loss", default="", help="robust loss kind:scale (huber | soft_l1 | cauchy, e.g. "
                     "cauchy:0.5), set on every rank's handle and on the single-handle comparison")
+    ap.add_argument("--free-intrinsics", type=int, default=0,
+                    help="DAB_INTR_* group bits refined on every handle (every rank sets the same mask); the "
+                    "result is compared with the single handle at --tol")
+    ap.add_argument("--expect-auto-refused", action="store_true",
+                    help="with --free-intrinsics: a rig whose tables do not fit the small-camera paths (135 "
+                    "extrinsics), so AUTO picks PCG on several ranks; every rank's dab_solve must return "
+                    "DAB_E_UNSUPPORTED, leave the parameters alone, and solve with the mask cleared")
     ap.add_argument("--covariance", action="store_true",
                     help="after the solve (--iters LM iterations of the exact step; 0 = none) every rank calls "
                     "dab_covariance: the camera arrays must be bitwise equal across the ranks and, like every "
@@ -104,6 +116,42 @@ def main():
             ok = int(failed.item()) == world and sched == 2
             sys.stdout.write(f"DIST_CHECK {'OK' if ok else 'FAIL'} timeout: {int(failed.item())}/{world} ranks "
                              f"failed closed, eval schedule {sched}, rank 0: {msg!r}\n")
+            sys.stdout.flush()
+        dist.destroy_process_group()
+        return
+
+    if a.expect_auto_refused:
+        # LINEAR_SOLVER_AUTO resolves to IMPLICIT_SCHUR_PCG only on several ranks and only when the
+        # camera system is not a small one: the refusal of free intrinsics must then come from the
+        # solver AUTO chose, on every rank, and leave the handle usable
+        glob = pkg.synth(kind=1, num_arcs=16, num_rings=120, num_points=1500, obs_per_point=6, seed=63)
+        mine = glob.copy().shard(rank, world)
+        s = pkg.Solver(dev, rank, world, uid, host_allreduce=gloo_allreduce if a.host_collective else None)
+        auto = pkg.options(max_num_iterations=3, linear_solver_type=pkg.DAB_LINEAR_SOLVER_AUTO)
+        msg, after = "", None
+        try:
+            s.set_problem(mine)
+            s.set_intrinsics_free(a.free_intrinsics or 7)
+            nfi = s.get_intrinsics_free()[1]
+            try:
+                s.solve(auto)
+            except RuntimeError as e:
+                msg = str(e)
+            untouched = (np.array_equal(mine.points, glob.points) and np.array_equal(mine.ext, glob.ext)
+                         and np.array_equal(s.get_intrinsics(), glob.intr))
+            s.set_intrinsics_free(None)
+            after = s.solve(auto)
+        finally:
+            s.close()
+        good = ("libdab error -6" in msg and "exact step" in msg and untouched and nfi == glob.intr.shape[0]
+                and after["linear_solver_type_used"] == pkg.DAB_LINEAR_SOLVER_IMPLICIT_SCHUR_PCG
+                and after["final_cost"] < after["initial_cost"])
+        ok = torch.tensor([1 if good else 0], dtype=torch.int32)
+        dist.all_reduce(ok)
+        if rank == 0:
+            sys.stdout.write(f"DIST_CHECK {'OK' if int(ok.item()) == world else 'FAIL'} auto refused: "
+                             f"{int(ok.item())}/{world} ranks, {nfi} free intrinsics, {glob.ext.shape[0]} extrinsics, "
+                             f"rank 0: {msg!r}, then solver {after['linear_solver_type_used']}\n")
             sys.stdout.flush()
         dist.destroy_process_group()
         return
@@ -171,7 +219,9 @@ def main():
              "auto": pkg.DAB_LINEAR_SOLVER_AUTO}
     solvers = [names[x] for x in a.solvers.split(",")]
     out = {}
-    for kind in ((a.config,) if a.config else ("bal", "rig")):
+    # free intrinsics: the rig only (the small BAL problem has 40 per-camera intrinsics, more than
+    # the 16 the exact step's border takes)
+    for kind in ((a.config,) if a.config else ("rig",) if a.free_intrinsics else ("bal", "rig")):
         if kind == "bal":
             glob = pkg.synth(kind=0, num_cameras=40, num_points=4000, obs_per_point=6, seed=61)
         elif kind == "rig":
@@ -195,6 +245,8 @@ def main():
                 if loss:
                     s1.set_loss(*loss)
                 s1.set_problem(g1)
+                if a.free_intrinsics:
+                    s1.set_intrinsics_free(a.free_intrinsics)
                 ropts = opts
                 if lst == pkg.DAB_LINEAR_SOLVER_AUTO:
                     # what AUTO must pick on several ranks: the exact step for small camera
@@ -202,7 +254,7 @@ def main():
                     want = (pkg.DAB_LINEAR_SOLVER_EXPLICIT_SCHUR if glob.ext.shape[0] <= 160
                             else pkg.DAB_LINEAR_SOLVER_IMPLICIT_SCHUR_PCG)
                     ropts = pkg.options(max_num_iterations=a.iters, linear_solver_type=want)
-                ref = (s1.solve(ropts), g1.points.copy(), g1.ext.copy())
+                ref = (s1.solve(ropts), g1.points.copy(), g1.ext.copy(), g1.intr.copy())
                 s1.close()
             dist.barrier()
             mine = glob.copy().shard(rank, world)
@@ -211,6 +263,8 @@ def main():
             if loss and not live:
                 s.set_loss(*loss)  # the same loss on every rank (include/dab.h)
             s.set_problem(mine)
+            if a.free_intrinsics:
+                s.set_intrinsics_free(a.free_intrinsics)  # the same mask on every rank (include/dab.h)
             sched = s.eval_fused()
             p2p = s.comm_p2p()
             summ = s.solve(opts)
@@ -222,8 +276,12 @@ def main():
             dist.all_reduce(ext, op=dist.ReduceOp.MAX)
             ext_min = torch.from_numpy(mine.ext.copy())
             dist.all_reduce(ext_min, op=dist.ReduceOp.MIN)
+            kk = torch.from_numpy(mine.intr.copy())
+            dist.all_reduce(kk, op=dist.ReduceOp.MAX)
+            kk_min = torch.from_numpy(mine.intr.copy())
+            dist.all_reduce(kk_min, op=dist.ReduceOp.MIN)
             if rank == 0:
-                rs, rp, re = ref
+                rs, rp, re, rk = ref
                 ca = [it["cost"] for it in summ["iterations"]]
                 cb = [it["cost"] for it in rs["iterations"]]
                 n = min(len(ca), len(cb))
@@ -237,6 +295,10 @@ def main():
                     dpts=float(np.abs(pts.numpy() - rp).max()),
                     dext=float(np.abs(ext.numpy() - re).max()),
                     ext_ranks_equal=bool(torch.equal(ext, ext_min)),
+                    dintr=float((np.abs(kk.numpy() - rk) / np.maximum(1.0, np.abs(rk))).max()) if rk.size else 0.0,
+                    intr_ranks_equal=bool(torch.equal(kk, kk_min)),
+                    intr_moved=float(np.abs(rk - glob.intr).max()) if rk.size else 0.0,
+                    num_parameters=(summ["num_parameters"], rs["num_parameters"]),
                     eval_schedule=sched, p2p=p2p,
                     solver_used=(summ["linear_solver_type_used"], rs["linear_solver_type_used"]))
         for h in live:
@@ -250,6 +312,8 @@ def main():
                or (auto_want is not None and k.endswith(f"_{pkg.DAB_LINEAR_SOLVER_AUTO}")
                    and v["solver_used"][0] != auto_want)
                or v["dext"] > 1e-6 or not v["ext_ranks_equal"]
+               or v["dintr"] > 1e-6 or not v["intr_ranks_equal"]
+               or (a.free_intrinsics and not v["intr_moved"] > 0.0)
                or (not k.startswith("rig") and v["eval_schedule"] != 2)  # BAL shards: the split fused pass
                or (a.expect_p2p and v["p2p"] != 1)
                or (a.expect_no_p2p and v["p2p"] != 0)
