@@ -116,6 +116,11 @@ class DabCovarianceInfo(C.Structure):
     ]
 
 
+class DabCovarianceIntrInfo(C.Structure):
+    _fields_ = [("num_free_intr", C.c_int32), ("num_free_scalars", C.c_int32),
+                ("border_ms", C.c_double), ("reserved", C.c_double)]
+
+
 COV_STATUS = {0: "OK", 1: "RANK_DEFICIENT"}
 
 
@@ -160,6 +165,8 @@ SIGNATURES = {
     "dab_covariance_options_init": (None, [C.POINTER(DabCovarianceOptions)]),
     "dab_covariance": (C.c_int, [C.c_void_p, C.POINTER(DabCovarianceOptions), _dp, _dp, _dp,
                                  C.POINTER(DabCovarianceInfo)]),
+    "dab_covariance_intrinsics": (C.c_int, [C.c_void_p, C.POINTER(DabCovarianceOptions), _dp, _dp, _dp, _dp,
+                                            C.POINTER(DabCovarianceInfo), C.POINTER(DabCovarianceIntrInfo)]),
     "dab_eval_residuals": (C.c_int, [C.c_void_p, _dp, _dp]),
     "dab_eval_jacobians": (C.c_int, [C.c_void_p, _dp, _dp]),
     "dab_filter": (C.c_int, [C.c_void_p, C.c_double, _dp, C.c_double, _u8p, _u8p, _ip, _ip]),

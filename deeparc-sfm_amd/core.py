@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import (DabOptions, DabProblem, DabSummary, DabIteration, DabSynthConfig,
-                   DabCovarianceOptions, DabCovarianceInfo, check, load_library)
+                   DabCovarianceOptions, DabCovarianceInfo, DabCovarianceIntrInfo, check, load_library)
 
 
 def _ptr(a, ct):
@@ -336,7 +336,7 @@ class Solver:
             self.problem.intr[...] = self.get_intrinsics()
         return summary_to_dict(s, its)
 
-    def covariance(self, points=True, ext=True, full=False, **opts):
+    def covariance(self, points=True, ext=True, full=False, intrinsics=False, **opts):
         """Sigma = (J^T J)^-1 at the parameters on the handle (dab_covariance; no sigma^2 factor:
         multiply by 2 info["cost"] / (num_residuals - num_parameters)). Returns a dict with
         `info`, `point_cov` (num_points, 3, 3) with NaN rows for unreferenced points, `ext_cov`
@@ -344,7 +344,17 @@ class Solver:
         is a union over ranks), and `ext_full` (6 nfe, 6 nfe) when full. When info["status"] is
         "RANK_DEFICIENT" the arrays are None: drop single-observation points (Problem.subset) or
         fix the scale gauge with one more constant extrinsic. Two library calls: the size and
-        rank query, then the arrays."""
+        rank query, then the arrays.
+
+        intrinsics=True: the free intrinsics of set_intrinsics_free are unknowns as well
+        (dab_covariance_intrinsics; the default call refuses a handle with a non-empty free set).
+        The dict gains `intr_cov` (nfi, 6, 6) over the slots (cx, cy, f0, f1, k0, k1) with zero
+        rows and columns for inactive slots, `intr_index` (the intrinsic of each block; None on a
+        shard whose referenced set is a union over ranks), `cam_full` (6 nfe + 6 nfi square:
+        extrinsics, then intrinsics) when full, and info's num_free_intr, num_free_scalars and
+        border_ms."""
+        if intrinsics:
+            return self._covariance_intrinsics(points, ext, full, opts)
         o = covariance_options(**opts)
         info = DabCovarianceInfo()
         check(self.lib.dab_covariance(self.h, C.byref(o), None, None, None, C.byref(info)), self.lib)
@@ -370,6 +380,51 @@ class Solver:
         return dict(info=d, point_cov=_unpack_sym(pc, 3) if ok and points else None,
                     ext_cov=_unpack_sym(ec, 6) if ok and ext else None, ext_index=idx,
                     ext_full=ef if ok and full else None)
+
+    def _ext_index(self, nfe):
+        pr = self.problem
+        if pr.freeze_camera:
+            return np.zeros(0, np.int32) if nfe == 0 else None
+        used = np.unique(np.concatenate([pr.obs_ext0, pr.obs_ext1[pr.obs_ext1 >= 0]]))
+        if pr.ext_const is not None:
+            used = used[pr.ext_const[used] == 0]
+        return used.astype(np.int32) if used.shape[0] == nfe else None
+
+    def _intr_index(self, nfi):
+        """The intrinsic of each block of intr_cov: referenced, with an active scalar selected."""
+        pr = self.problem
+        groups = self.get_intrinsics_free()[0].astype(np.int64)
+        if pr.freeze_camera:
+            groups[:] = 0
+        has = np.stack([groups & 1, groups & 1, groups & 2, (groups & 2) * (pr.intr_nf == 2),
+                        (groups & 4) * (pr.intr_nk >= 1), (groups & 4) * (pr.intr_nk >= 2)], axis=1) != 0
+        ref = np.zeros(groups.shape[0], bool)
+        ref[pr.obs_intr] = True
+        idx = np.flatnonzero(has.any(axis=1) & ref).astype(np.int32)
+        return idx if idx.shape[0] == nfi else None
+
+    def _covariance_intrinsics(self, points, ext, full, opts):
+        o = covariance_options(**opts)
+        info, zinfo = DabCovarianceInfo(), DabCovarianceIntrInfo()
+        call = self.lib.dab_covariance_intrinsics
+        check(call(self.h, C.byref(o), None, None, None, None, C.byref(info), C.byref(zinfo)), self.lib)
+        nfe, nfi, npts = info.num_free_ext, zinfo.num_free_intr, int(self.problem.points.shape[0])
+        n2 = 6 * nfe + 6 * nfi
+        pc = np.zeros((npts, 6)) if points else None
+        ec = np.zeros((nfe, 21)) if ext else None
+        zc = np.zeros((nfi, 21))
+        cf = np.zeros((n2, n2)) if full else None
+        if info.status == 0:
+            check(call(self.h, C.byref(o), _ptr(pc, C.c_double), _ptr(ec, C.c_double), _ptr(zc, C.c_double),
+                       _ptr(cf, C.c_double), C.byref(info), C.byref(zinfo)), self.lib)
+        d = {k: getattr(info, k) for k, _ in DabCovarianceInfo._fields_}
+        d.update({k: getattr(zinfo, k) for k in ("num_free_intr", "num_free_scalars", "border_ms")})
+        d["status"] = _abi.COV_STATUS.get(info.status, str(info.status))
+        ok = info.status == 0
+        return dict(info=d, point_cov=_unpack_sym(pc, 3) if ok and points else None,
+                    ext_cov=_unpack_sym(ec, 6) if ok and ext else None, ext_index=self._ext_index(nfe),
+                    intr_cov=_unpack_sym(zc, 6) if ok else None, intr_index=self._intr_index(nfi),
+                    cam_full=cf if ok and full else None)
 
     def residuals(self):
         r = np.zeros((self.problem.num_obs, 2))

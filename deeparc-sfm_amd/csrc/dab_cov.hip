@@ -28,12 +28,18 @@ constexpr int CB = 64;    // block size of the blocked inverse
 constexpr int CLS = 65;   // LDS row stride of the diagonal-block kernel
 typedef double dbl4 __attribute__((ext_vector_type(4)));
 
-// min / max / non-finite count of the factor's squared diagonal -> out[3] (one work-group)
-__global__ __launch_bounds__(256) void k_cov_diag_minmax(int n, const double* __restrict__ Ld,
-                                                         double* __restrict__ out) {
+// min / max / non-finite count of the factor's squared diagonal -> out[3] (one work-group).
+// ACT: rows n_ext .. n - 1 are the six slots of the free intrinsics (act[i]: the active bits of
+// free intrinsic i); the unit rows of inactive slots are left out.
+template <bool ACT>
+__device__ __forceinline__ void cov_diag_minmax(int n, int n_ext, const int* __restrict__ act,
+                                                const double* __restrict__ Ld, double* __restrict__ out) {
   __shared__ double smin[256], smax[256], sbad[256];
   double mn = INFINITY, mx = 0.0, bad = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) {
+    if constexpr (ACT) {
+      if (i >= n_ext && !((act[(i - n_ext) / 6] >> ((i - n_ext) % 6)) & 1)) continue;
+    }
     const double d = Ld[(size_t)kCholBlk * (i / CB) + kCholBlkL + (i % CB) * (CB + 1)];
     const double d2 = d * d;
     if (!isfinite(d2) || !(d > 0.0)) {
@@ -60,6 +66,15 @@ __global__ __launch_bounds__(256) void k_cov_diag_minmax(int n, const double* __
     out[1] = smax[0];
     out[2] = sbad[0];
   }
+}
+__global__ __launch_bounds__(256) void k_cov_diag_minmax(int n, const double* __restrict__ Ld,
+                                                         double* __restrict__ out) {
+  cov_diag_minmax<false>(n, n, nullptr, Ld, out);
+}
+__global__ __launch_bounds__(256) void k_cov_diag_minmax_act(int n, int n_ext, const int* __restrict__ act,
+                                                             const double* __restrict__ Ld,
+                                                             double* __restrict__ out) {
+  cov_diag_minmax<true>(n, n_ext, act, Ld, out);
 }
 
 // Z_ii = L_ii^-1. Thread c owns column c of the block: z_r = (delta_rc - sum_{c<=k<r} L_rk z_k)
@@ -352,6 +367,21 @@ __global__ __launch_bounds__(256) void k_cov_unscale(int n, const double* __rest
   const size_t i = t / n, j = t - i * n;
   C[i * ldc + j] *= sc[i] * sc[j];
 }
+// The same over the bordered system of n = n_ext + 6 nfi rows, s = (s_c, s_z); the rows and
+// columns of inactive intrinsic slots (s_z = 0: known exactly) are written as +0
+__global__ __launch_bounds__(256) void k_cov_unscale_z(int n, int n_ext, const double* __restrict__ sc,
+                                                       const double* __restrict__ sz, const int* __restrict__ act,
+                                                       double* __restrict__ C, int ldc) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (size_t)n * n) return;
+  const int i = (int)(t / n), j = (int)(t - (size_t)i * n);
+  const bool zi = i >= n_ext, zj = j >= n_ext;
+  const bool off = (zi && !((act[(i - n_ext) / 6] >> ((i - n_ext) % 6)) & 1)) ||
+                   (zj && !((act[(j - n_ext) / 6] >> ((j - n_ext) % 6)) & 1));
+  const double si = zi ? sz[i - n_ext] : sc[i], sj = zj ? sz[j - n_ext] : sc[j];
+  double* c = C + (size_t)i * ldc + j;
+  *c = off ? 0.0 : *c * (si * sj);
+}
 // the 6x6 diagonal blocks, upper-packed -> out[NC][21]
 __global__ __launch_bounds__(256) void k_cov_ext_blocks(int NC, const double* __restrict__ C, int ldc,
                                                         double* __restrict__ out) {
@@ -381,6 +411,10 @@ void launch_cov_inverse(hipStream_t s, int n, const double* L, int lda, const do
   k_cov_ztz<<<dim3(nb, nb), 256, 0, s>>>(n, Z, ldz, C, ldc);
 }
 
+void launch_cov_diag_minmax_act(hipStream_t s, int n, int n_ext, const int* act, const double* Ld, double* out) {
+  k_cov_diag_minmax_act<<<1, 256, 0, s>>>(n, n_ext, act, Ld, out);
+}
+
 int cov_rank_grid(int NP) { return std::max(1, std::min(256, (NP + 255) / 256)); }
 void launch_cov_point_rank(hipStream_t s, int NP, const double* V, const double* scale_p, double thr, double* ratio,
                            double* partial, int grid) {
@@ -393,6 +427,28 @@ void launch_cov_points(hipStream_t s, const DevView& v, bool with_cams, const do
   const int g = (v.NP + 255) / 256;
   if (with_cams) k_cov_merge<<<g, 256, 0, s>>>(v, Y, Ym, mcam, mcnt);
   k_cov_points<<<g, 256, 0, s>>>(v, with_cams ? 1 : 0, PU, Ym, mcam, mcnt, C, ldc, out);
+}
+
+void launch_cov_points_z(hipStream_t s, const DevView& v, bool with_cams, const double* points,
+                         const double* camtab, const double* PU, const double* sz, const int2* meta,
+                         const double* Y, double* Ym, int* mcam, int* mcnt, const int* rbase, double* rec, int* rcam,
+                         int* rcnt, const double* C, int ldc, double* out) {
+  if (v.NP <= 0) return;
+  const int g = (v.NP + 255) / 256;
+  if (with_cams) k_cov_merge<<<g, 256, 0, s>>>(v, Y, Ym, mcam, mcnt);
+  launch_cov_gz(s, v, points, camtab, PU, sz, meta, with_cams, rbase, Ym, mcam, mcnt, rec, rcam, rcnt);
+  // k_cov_points reads of the view only NP and where each point's records begin
+  DevView vr = v;
+  vr.pt_ent_ptr = rbase;
+  k_cov_points<<<g, 256, 0, s>>>(vr, 1, PU, rec, rcam, rcnt, C, ldc, out);
+}
+
+void launch_cov_unscale_z(hipStream_t s, int NC, int nfi, const double* scale_c, const double* sz, const int* act,
+                          double* C, int ldc, double* blocks) {
+  const size_t n = (size_t)6 * (NC + nfi);
+  if (n == 0) return;
+  k_cov_unscale_z<<<(unsigned)((n * n + 255) / 256), 256, 0, s>>>((int)n, 6 * NC, scale_c, sz, act, C, ldc);
+  if (blocks) k_cov_ext_blocks<<<(21 * (NC + nfi) + 255) / 256, 256, 0, s>>>(NC + nfi, C, ldc, blocks);
 }
 
 void launch_cov_unscale(hipStream_t s, int NC, const double* scale_c, double* C, int ldc, double* ext_cov) {

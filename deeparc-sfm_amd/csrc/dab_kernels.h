@@ -451,6 +451,24 @@ void launch_cov_points(hipStream_t s, const DevView& v, bool with_cams, const do
                        double* Ym, int* mcam, int* mcnt, const double* C, int ldc, double* out);
 // C <- s_c C s_c' in place, then its 6x6 diagonal blocks upper-packed -> ext_cov[NC][21] (nullable)
 void launch_cov_unscale(hipStream_t s, int NC, const double* scale_c, double* C, int ldc, double* ext_cov);
+// dab_covariance_intrinsics: the same three over the bordered system of n = 6 NC + 6 nfi rows.
+// The diagonal test leaves out the unit rows of inactive intrinsic slots (act[nfi], rows >= n_ext).
+void launch_cov_diag_minmax_act(hipStream_t s, int n, int n_ext, const int* act, const double* Ld, double* out);
+// The fold-back over the point's merged camera records and one record Gz_p,i per free intrinsic
+// it sees ("camera" NC + i, k_cov_gz): rbase[NP + 1] = where each point's records begin in rec
+// [.][18] / rcam (its entries + the free intrinsics it sees, ptmask); rcnt [NP]. Ym / mcam / mcnt:
+// k_cov_merge's scratch as in launch_cov_points. C: the scaled inverse of the bordered system.
+void launch_cov_gz(hipStream_t s, const DevView& v, const double* points, const double* camtab, const double* PU,
+                   const double* sz, const int2* meta, bool with_cams, const int* rbase, const double* Ym,
+                   const int* mcam, const int* mcnt, double* rec, int* rcam, int* rcnt);
+void launch_cov_points_z(hipStream_t s, const DevView& v, bool with_cams, const double* points,
+                         const double* camtab, const double* PU, const double* sz, const int2* meta,
+                         const double* Y, double* Ym, int* mcam, int* mcnt, const int* rbase, double* rec, int* rcam,
+                         int* rcnt, const double* C, int ldc, double* out);
+// C <- s C s with s = (s_c, s_z), inactive slots' rows and columns +0; then the 6x6 diagonal
+// blocks upper-packed -> blocks[NC + nfi][21] (nullable): extrinsics, then intrinsics
+void launch_cov_unscale_z(hipStream_t s, int NC, int nfi, const double* scale_c, const double* sz, const int* act,
+                          double* C, int ldc, double* blocks);
 
 int grid_for(int n, int block, int cap);
 

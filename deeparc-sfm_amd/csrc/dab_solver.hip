@@ -462,6 +462,13 @@ struct dab_handle {
   double *d_covZ = nullptr, *d_cov_pts = nullptr, *d_cov_ext = nullptr, *d_cov_stat = nullptr;
   int* d_cov_idx = nullptr;  // [NE] camera of each merged record | [NP] records per point
   hipEvent_t cov_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  // dab_covariance_intrinsics (lazy; freed by dab_set_problem): Z of the bordered system [n'][ldz],
+  // the fold-back's records [cap][18] and [camera of each record cap | records per point NP |
+  // first record of each point NP + 1]; events around the border rows
+  double *d_covZz = nullptr, *d_cov_rec = nullptr;
+  int* d_cov_ridx = nullptr;
+  size_t covZz_cap = 0, cov_rec_cap = 0;
+  hipEvent_t cov_ev_z[2] = {nullptr, nullptr};
   float *d_Y32c = nullptr, *d_Y32p = nullptr;                                 // pcg_fp32 (lazy)
   double* d_camred = nullptr;  // [Ucc NC*21 | gc NC*6 | Ux ncross*36] (all-reduced)
   double* d_partial = nullptr; // chunk partials (max of chunk counts * 36)
@@ -570,6 +577,8 @@ struct dab_handle {
     if (ev2) (void)hipEventDestroy(ev2);
     if (ev3) (void)hipEventDestroy(ev3);
     for (hipEvent_t e : cov_ev)
+      if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : cov_ev_z)
       if (e) (void)hipEventDestroy(e);
     for (auto& e : bench_ev)
       for (hipEvent_t x : e) (void)hipEventDestroy(x);
@@ -2292,12 +2301,16 @@ static int set_problem_impl(dab_handle* h, const dab_problem* p) {
   HIP_OK(hipSetDevice(h->device));
   HIP_OK(hipStreamSynchronize(h->stream));
   h->dev.drop(h->d_covZ);  // n x n: back to the device, not into the pool
+  h->dev.drop(h->d_covZz);
   h->dev.release();
   // lazily allocated buffers went with the release: clear their pointers so that the next
   // use allocates again (a stale pointer would be written after its memory was freed)
   h->d_Yrec = nullptr;
   h->d_covZ = h->d_cov_pts = h->d_cov_ext = h->d_cov_stat = nullptr;
   h->d_cov_idx = nullptr;
+  h->d_covZz = h->d_cov_rec = nullptr;
+  h->d_cov_ridx = nullptr;
+  h->covZz_cap = h->cov_rec_cap = 0;
   h->d_Y32c = h->d_Y32p = nullptr;
   h->d_Jfull = nullptr;
   h->have_problem = false;
@@ -3371,6 +3384,55 @@ extern "C" int dab_get_loss(dab_handle* h, int32_t* loss_type, double* scale) {
   return 0;
 }
 
+// The system with the block z (nfi > 0): the handle's dense buffer of n' = 6 NC + 6 nfi rows (+
+// the rhs row) at ldz, the solution and border-sum buffers, which free intrinsics each point sees
+// (k_intr_ptmask) and the border kernels' partials. dab_solve and dab_covariance_intrinsics.
+static int intr_system_buffers(dab_handle* h, int nfi) {
+  if (nfi <= 0) return 0;
+  const int n2 = 6 * h->NC + 6 * nfi;
+  h->ldz = ((n2 + 1 + 7) / 8) * 8;
+  if (h->ldz % 512 == 0) h->ldz += 8;
+  const size_t need = (size_t)(n2 + 1) * h->ldz;
+  if (need > h->Sz_cap) {
+    h->dev.drop(h->d_Sz);
+    h->d_Sz = nullptr;
+    h->Sz_cap = 0;
+    CHECK_RC(h->dev.alloc(&h->d_Sz, need));
+    h->Sz_cap = need;
+  }
+  if (!h->d_yz) {
+    CHECK_RC(h->dev.alloc(&h->d_yz, (size_t)6 * h->NC + 6 * kIntrFreeMax));
+    CHECK_RC(h->dev.alloc(&h->d_bsum, (size_t)6 * kIntrFreeMax * (6 * (size_t)h->NC + 6 * kIntrFreeMax + 1)));
+    CHECK_RC(h->dev.alloc(&h->d_ptmask, (size_t)std::max(1, h->NP)));
+  }
+  launch_intr_ptmask(h->stream, h->view, h->d_intr_meta, h->d_ptmask);
+  int spg = 1;
+  const size_t bneed = (size_t)intr_border_groups(h->view.nslice, h->NC, nfi, &spg) * (size_t)(6 * nfi) * (n2 + 1);
+  if (bneed > h->bpart_cap) {
+    h->dev.drop(h->d_bpart);
+    h->d_bpart = nullptr;
+    h->bpart_cap = 0;
+    CHECK_RC(h->dev.alloc(&h->d_bpart, bneed));
+    h->bpart_cap = bneed;
+  }
+  return 0;
+}
+// The rows of the block z of S (n' x n' at ld, the leading n x n part and the rhs row n built by
+// either assembly): the rhs moves to row n', then the border sums (one point-major pass),
+// all-reduced and scattered into S
+static int intr_border_rows(dab_handle* h, int nfi, const StepScalars& sc, double* S, int ld) {
+  if (nfi <= 0) return 0;
+  hipStream_t s = h->stream;
+  const int n = 6 * h->NC, n2 = n + 6 * nfi;
+  HIP_OK(hipMemcpyAsync(S + (size_t)n2 * ld, S + (size_t)n * ld, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice,
+                        s));
+  launch_intr_border(s, h->view, h->d_points, h->d_camtab, h->d_scale_c, h->d_L, h->d_q, h->d_sz, h->d_intr_meta,
+                     h->d_ptmask, nfi, h->d_bpart, h->d_bsum, h->knobs.intr_border_lds != 0);
+  CHECK_RC(h->allreduce(h->d_bsum, (size_t)(6 * nfi) * (size_t)(n2 + 1), ncclSum));
+  launch_intr_scatter(s, n, nfi, h->d_bsum, h->d_zg, h->d_sz, h->d_intr_act, sc, S, ld);
+  return 0;
+}
+
 static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum) {
   clear_error();
   if (!h || !h->have_problem) return set_error(DAB_E_STATE, "no problem set");
@@ -3407,33 +3469,7 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
   const double tp1 = now_s();
   // the system with the block z: its own dense buffer of n' = 6 NC + 6 nfi rows (+ rhs row)
   const int n2 = 6 * h->NC + 6 * nfi;
-  if (nfi > 0) {
-    h->ldz = ((n2 + 1 + 7) / 8) * 8;
-    if (h->ldz % 512 == 0) h->ldz += 8;
-    const size_t need = (size_t)(n2 + 1) * h->ldz;
-    if (need > h->Sz_cap) {
-      h->dev.drop(h->d_Sz);
-      h->d_Sz = nullptr;
-      h->Sz_cap = 0;
-      CHECK_RC(h->dev.alloc(&h->d_Sz, need));
-      h->Sz_cap = need;
-    }
-    if (!h->d_yz) {
-      CHECK_RC(h->dev.alloc(&h->d_yz, (size_t)6 * h->NC + 6 * kIntrFreeMax));
-      CHECK_RC(h->dev.alloc(&h->d_bsum, (size_t)6 * kIntrFreeMax * (6 * (size_t)h->NC + 6 * kIntrFreeMax + 1)));
-      CHECK_RC(h->dev.alloc(&h->d_ptmask, (size_t)std::max(1, h->NP)));
-    }
-    launch_intr_ptmask(h->stream, h->view, h->d_intr_meta, h->d_ptmask);
-    int spg = 1;
-    const size_t bneed = (size_t)intr_border_groups(h->view.nslice, h->NC, nfi, &spg) * (size_t)(6 * nfi) * (n2 + 1);
-    if (bneed > h->bpart_cap) {
-      h->dev.drop(h->d_bpart);
-      h->d_bpart = nullptr;
-      h->bpart_cap = 0;
-      CHECK_RC(h->dev.alloc(&h->d_bpart, bneed));
-      h->bpart_cap = bneed;
-    }
-  }
+  CHECK_RC(intr_system_buffers(h, nfi));
   double* const S_ = nfi > 0 ? h->d_Sz : h->d_S;
   const int ld_ = nfi > 0 ? h->ldz : h->lds;
   double* const yc_ = nfi > 0 ? h->d_yz : h->d_yc;
@@ -3479,16 +3515,7 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
   const bool in_global = true;  (void)in_global;
   // the rows of the block z: the rhs moves to row n', then the border sums (one point-major pass,
   // whichever assembly built the leading n x n part), all-reduced and scattered into S
-  auto intr_border = [&](const StepScalars& sc) -> int {
-    if (nfi <= 0) return 0;
-    HIP_OK(hipMemcpyAsync(S_ + (size_t)n2 * ld_, S_ + (size_t)n * ld_, sizeof(double) * (size_t)n,
-                          hipMemcpyDeviceToDevice, s));
-    launch_intr_border(s, v, h->d_points, h->d_camtab, h->d_scale_c, h->d_L, h->d_q, h->d_sz, h->d_intr_meta,
-                       h->d_ptmask, nfi, h->d_bpart, h->d_bsum, h->knobs.intr_border_lds != 0);
-    CHECK_RC(h->allreduce(h->d_bsum, (size_t)(6 * nfi) * (size_t)(n2 + 1), ncclSum));
-    launch_intr_scatter(s, n, nfi, h->d_bsum, h->d_zg, h->d_sz, h->d_intr_act, sc, S_, ld_);
-    return 0;
-  };
+  auto intr_border = [&](const StepScalars& sc) -> int { return intr_border_rows(h, nfi, sc, S_, ld_); };
 
   // ---- iteration 0 ----
   // a solve starts with a clean sticky error word (a timed-out wait of an earlier call was
@@ -3798,14 +3825,23 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
 // PU_p = s_p L_p^-T, Y_e = (s_c ∘ Jc^T Jp) PU_p and C = (scaled S)^-1:
 //   Sigma_cc' = s_c C_cc' s_c',  Sigma_pp = PU_p (I + sum_{e,e'} Y_e^T C_c(e)c(e') Y_e') PU_p^T.
 // The LM kernels run unchanged with radius = +inf: their sqrt(clamp(d) / radius) is exactly 0.
+//
+// with_intr (dab_covariance_intrinsics): the free intrinsics of the handle's mask join the camera
+// system as in the exact step, S' of n' = 6 NC + 6 nfi rows in the handle's z buffer with the
+// border rows of one undamped LM step; C' = S'^-1, s = (s_c, s_z), and a point's fold-back gains
+// one record Gz_p,i per free intrinsic it sees (k_cov_gz). With nfi = 0 every launch and buffer
+// is dab_covariance's. ext_full: [n'][n'] then, intr_cov [nfi][21].
 static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, double* point_cov, double* ext_cov,
-                           double* ext_full, dab_covariance_info* info) {
-  if (h && h->have_problem && intr_mask_any(h)) {
+                           double* intr_cov, double* ext_full, dab_covariance_info* info,
+                           dab_covariance_intr_info* zinfo, bool with_intr) {
+  if (!with_intr && h && h->have_problem && intr_mask_any(h)) {
     // free intrinsics are not part of the covariance: it would report them as exactly known
     int nfi_cov = 0;
     HIP_OK(hipSetDevice(h->device));
     CHECK_RC(intr_free_set(h, true, &nfi_cov));
-    if (nfi_cov > 0) return set_error(DAB_E_UNSUPPORTED, "dab_covariance with free intrinsics is not supported");
+    if (nfi_cov > 0)
+      return set_error(DAB_E_UNSUPPORTED,
+                       "dab_covariance with free intrinsics is not supported (dab_covariance_intrinsics is)");
   }
   clear_error();
   if (!h) return set_error(DAB_E_INVALID, "null handle");
@@ -3814,16 +3850,31 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
   else dab_covariance_options_init(&opt);
   if (!(std::isfinite(opt.min_pivot_ratio) && opt.min_pivot_ratio > 0.0))
     return set_error(DAB_E_INVALID, "min_pivot_ratio must be finite and > 0");
-  if (!info && !point_cov && !ext_cov && !ext_full) return set_error(DAB_E_INVALID, "null info and null arrays");
+  if (!info && !point_cov && !ext_cov && !intr_cov && !ext_full)
+    return set_error(DAB_E_INVALID, "null info and null arrays");
   if (!h->have_problem) return set_error(DAB_E_STATE, "no problem set");
   HIP_OK(hipSetDevice(h->device));
+  // free intrinsics: dab_solve's rule and refusals, before anything on the handle changes
+  int nfi = 0, nz_scal = 0;
+  if (with_intr && intr_mask_any(h)) {
+    CHECK_RC(intr_free_set(h, true, &nfi, &nz_scal));
+    if (nfi > kIntrFreeMax) return set_error(DAB_E_UNSUPPORTED, "more than 16 free intrinsics");
+    if (nfi > 0 && h->NC == 0) return set_error(DAB_E_UNSUPPORTED, "free intrinsics need a free extrinsic");
+  }
   hipStream_t s = h->stream;
   const DevView& v = h->view;
   const int NP = h->NP;
   if (h->NC > 0) CHECK_RC(build_schur_tables(h));
-  const int NC = h->NC, n = 6 * NC;
-  if (NC > 0 && chol_prepare(h->chol, s, n, h->d_S, h->lds, h->d_yc, h->d_flags + 1) != 0)
+  const int NC = h->NC, n = 6 * NC, n2 = n + 6 * nfi;
+  CHECK_RC(intr_system_buffers(h, nfi));
+  double* const S_ = nfi > 0 ? h->d_Sz : h->d_S;
+  const int ld_ = nfi > 0 ? h->ldz : h->lds;
+  double* const yc_ = nfi > 0 ? h->d_yz : h->d_yc;
+  if (NC > 0 && chol_prepare(h->chol, s, n2, S_, ld_, yc_, h->d_flags + 1) != 0)
     return set_error(DAB_E_DEVICE, "dense Cholesky set-up failed");
+  dab_covariance_intr_info zout{};
+  zout.num_free_intr = nfi;
+  zout.num_free_scalars = nz_scal;
   dab_covariance_info out{};
   out.status = DAB_COV_OK;
   out.num_free_ext = NC;
@@ -3831,10 +3882,13 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
   out.first_deficient_point = -1;
   out.schur_assembly = h->schur_tiles ? DAB_SCHUR_TILES : DAB_SCHUR_PAIRS;
   out.num_residuals = 2 * h->N;
-  out.num_parameters = 3 * NP + 6 * NC;
+  out.num_parameters = 3 * NP + 6 * NC + nz_scal;
   out.point_pivot_ratio_min = out.camera_pivot_ratio = std::numeric_limits<double>::quiet_NaN();
   for (hipEvent_t& e : h->cov_ev)
     if (!e) HIP_OK(hipEventCreate(&e));
+  if (nfi > 0)
+    for (hipEvent_t& e : h->cov_ev_z)
+      if (!e) HIP_OK(hipEventCreate(&e));
   const int rgrid = cov_rank_grid(NP);
   if (!h->d_cov_stat) CHECK_RC(h->dev.alloc(&h->d_cov_stat, (size_t)8 + 2 * (size_t)rgrid));
   double* d_stat = h->d_cov_stat;         // [0] deficient points, [4..6] diagonal min / max / bad
@@ -3844,8 +3898,10 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
   HIP_OK(hipMemsetAsync(h->d_scal + S_XERR, 0, sizeof(double), s));
   HIP_OK(hipEventRecord(h->cov_ev[0], s));
   CHECK_RC(eval_jacobian_and_blocks(h, false));
+  if (nfi > 0) CHECK_RC(intr_eval(h));
   k_scale_points<<<grid_for(3 * NP, 256, 1 << 20), 256, 0, s>>>(NP, h->d_V, h->d_scale_p, opt.jacobi_scaling);
   if (NC > 0) k_scale_cams<<<grid_for(6 * NC, 256, 1 << 20), 256, 0, s>>>(NC, h->ug(), h->d_scale_c, opt.jacobi_scaling);
+  launch_intr_scale(s, nfi, h->d_zg, h->d_intr_act, h->d_sz, opt.jacobi_scaling);
   HIP_OK(hipEventRecord(h->cov_ev[1], s));
   CHECK_RC(read_scalars(h));
   if (h->h_scal[S_COST_BAD] != 0.0)
@@ -3885,7 +3941,12 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
       HIP_OK(hipEventElapsedTime(&ms, h->cov_ev[3], h->cov_ev[4]));
       out.points_ms = ms;
     }
+    if (nfi > 0 && last != h->cov_ev[1]) {
+      HIP_OK(hipEventElapsedTime(&ms, h->cov_ev_z[0], h->cov_ev_z[1]));
+      zout.border_ms = ms;
+    }
     if (info) *info = out;
+    if (zinfo) *zinfo = zout;
     return 0;
   };
   if (hstat[0] > 0.0) {
@@ -3916,9 +3977,9 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
     launch_schur_sum_tiles(s, a, h->d_sblk);
     CHECK_RC(h->allreduce(h->d_sblk, (size_t)a.nelem, ncclSum));
     CHECK_RC(h->allreduce_u64(reinterpret_cast<uint64_t*>(h->d_rfx), (size_t)6 * NC));
-    HIP_OK(hipMemsetAsync(h->d_S, 0, sizeof(double) * (size_t)(n + 1) * h->lds, s));
-    launch_schur_unpack(s, NC, h->d_sblk, h->d_rfx, h->d_kx, a.kq, h->d_S, h->lds, h->ybc());
-    launch_s_add_u(s, NC, h->ug(), h->ncross, h->d_cross_cam, h->Ux(), h->d_scale_c, sc, h->ybc(), h->d_S, h->lds);
+    HIP_OK(hipMemsetAsync(S_, 0, sizeof(double) * (size_t)(n + 1) * ld_, s));
+    launch_schur_unpack(s, NC, h->d_sblk, h->d_rfx, h->d_kx, a.kq, S_, ld_, h->ybc());
+    launch_s_add_u(s, NC, h->ug(), h->ncross, h->d_cross_cam, h->Ux(), h->d_scale_c, sc, h->ybc(), S_, ld_);
     // the point kernel reads per-entry records: the tile path keeps per-(point, camera) sums only
     if (!h->d_Yrec) CHECK_RC(h->dev.alloc(&h->d_Yrec, (size_t)kYRec * std::max(1, h->NE)));
     if (point_cov)
@@ -3929,21 +3990,27 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
     launch_entry_y(s, v, h->d_points, h->d_camtab, h->d_scale_c, h->d_L, yb, false, h->d_Yrec);
     const bool direct = h->world == 1;
     launch_s_blocks(s, h->nblk, h->d_blk_pair_beg, h->d_pairs, nullptr, h->NE, h->packed(), h->d_Yrec,
-                    direct ? h->d_S : nullptr, h->lds, h->d_blk_cam, h->nzero, h->d_blk_zero);
+                    direct ? S_ : nullptr, ld_, h->d_blk_cam, h->nzero, h->d_blk_zero);
     launch_cam_rhs_partial(s, v, h->nchunk, h->d_chunk_beg, h->d_Yrec, h->d_q, h->d_partial, true);
     launch_seg_final(s, NC, 6, h->d_seg_chunk, h->d_partial, h->ybc(), h->max_seg_chunks);
     if (direct) {
-      launch_s_add_u(s, NC, h->ug(), h->ncross, h->d_cross_cam, h->Ux(), h->d_scale_c, sc, h->ybc(), h->d_S, h->lds);
+      launch_s_add_u(s, NC, h->ug(), h->ncross, h->d_cross_cam, h->Ux(), h->d_scale_c, sc, h->ybc(), S_, ld_);
     } else {
       CHECK_RC(h->allreduce(h->d_spack, h->spack_count(), ncclSum));
       launch_s_unpack(s, NC, h->nblk, h->d_blk_cam, h->packed(), h->ug(), h->ncross, h->d_cross_cam, h->Ux(),
-                      h->d_scale_c, sc, h->ybc(), h->d_S, h->lds);
+                      h->d_scale_c, sc, h->ybc(), S_, ld_);
     }
   }
   if (NC > 0) {
-    if (chol_factor_solve(h->chol, s, n, h->d_S, h->lds, h->d_yc, h->d_flags + 1) != 0)
+    if (nfi > 0) {
+      HIP_OK(hipEventRecord(h->cov_ev_z[0], s));
+      CHECK_RC(intr_border_rows(h, nfi, sc, S_, ld_));
+      HIP_OK(hipEventRecord(h->cov_ev_z[1], s));
+    }
+    if (chol_factor_solve(h->chol, s, n2, S_, ld_, yc_, h->d_flags + 1) != 0)
       return set_error(DAB_E_DEVICE, "dense Cholesky launch failed");
-    launch_cov_diag_minmax(s, n, chol_diag_blocks(h->chol), d_stat + 4);
+    if (nfi > 0) launch_cov_diag_minmax_act(s, n2, n, h->d_intr_act, chol_diag_blocks(h->chol), d_stat + 4);
+    else launch_cov_diag_minmax(s, n, chol_diag_blocks(h->chol), d_stat + 4);
   }
   HIP_OK(hipEventRecord(h->cov_ev[2], s));
   HIP_OK(hipMemcpyAsync(hstat + 4, d_stat + 4, sizeof(double) * 3, hipMemcpyDeviceToHost, s));
@@ -3961,11 +4028,22 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
       return finish(h->cov_ev[2]);
     }
   }
-  if (!point_cov && !ext_cov && !ext_full) return finish(h->cov_ev[2]);  // the size / rank query
+  if (!point_cov && !ext_cov && !intr_cov && !ext_full) return finish(h->cov_ev[2]);  // the size / rank query
 
   // ---- C = S^-1 from the factor, the point blocks, the unscaled camera part ----
-  const bool want_c = NC > 0 && (point_cov || ext_cov || ext_full);
-  if (want_c) {
+  const bool want_c = NC > 0 && (point_cov || ext_cov || intr_cov || ext_full);
+  if (want_c && nfi > 0) {
+    // the second n' x n' buffer (n' changes with the free set: kept while it fits)
+    const size_t need = (size_t)n2 * ld_;
+    if (need > h->covZz_cap) {
+      h->dev.drop(h->d_covZz);
+      h->d_covZz = nullptr;
+      h->covZz_cap = 0;
+      CHECK_RC(h->dev.alloc(&h->d_covZz, need));
+      h->covZz_cap = need;
+    }
+    launch_cov_inverse(s, n2, S_, ld_, chol_diag_blocks(h->chol), h->d_covZz, ld_, S_, ld_);
+  } else if (want_c) {
     if (!h->d_covZ) CHECK_RC(h->dev.alloc(&h->d_covZ, (size_t)n * h->lds));
     launch_cov_inverse(s, n, h->d_S, h->lds, chol_diag_blocks(h->chol), h->d_covZ, h->lds, h->d_S, h->lds);
   }
@@ -3973,18 +4051,54 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
   if (point_cov) {
     if (!h->d_cov_pts) CHECK_RC(h->dev.alloc(&h->d_cov_pts, (size_t)6 * std::max(1, NP)));
     if (!h->d_cov_idx) CHECK_RC(h->dev.alloc(&h->d_cov_idx, (size_t)std::max(1, h->NE) + (size_t)std::max(1, NP)));
-    // d_Y (the step's camera-major Y planes, unused on this route) takes the merged records
-    launch_cov_points(s, v, NC > 0 && h->NE > 0, h->d_L, h->d_Yrec, h->d_Y, h->d_cov_idx,
-                      h->d_cov_idx + std::max(1, h->NE), h->d_S, h->lds, h->d_cov_pts);
+    if (nfi > 0) {
+      // where each point's records begin: its entries, then the free intrinsics it sees
+      std::vector<int> ptmask((size_t)std::max(1, NP)), ent_ptr((size_t)NP + 1), rbase((size_t)NP + 1);
+      HIP_OK(hipMemcpyAsync(ptmask.data(), h->d_ptmask, sizeof(int) * (size_t)NP, hipMemcpyDeviceToHost, s));
+      HIP_OK(hipMemcpyAsync(ent_ptr.data(), h->d_pt_ent_ptr, sizeof(int) * ((size_t)NP + 1), hipMemcpyDeviceToHost, s));
+      HIP_OK(hipStreamSynchronize(s));
+      long long nz_rec = 0;
+      for (int p = 0; p < NP; ++p) {
+        rbase[(size_t)p] = (int)(ent_ptr[(size_t)p] + nz_rec);
+        nz_rec += __builtin_popcount((unsigned)ptmask[(size_t)p]);
+      }
+      const long long total = (long long)ent_ptr[(size_t)NP] + nz_rec;
+      if (total > INT_MAX) return set_error(DAB_E_UNSUPPORTED, "too many fold-back records for 32-bit indices");
+      rbase[(size_t)NP] = (int)total;
+      const size_t cap = (size_t)std::max<long long>(1, total);
+      if (cap > h->cov_rec_cap) {
+        h->dev.drop(h->d_cov_rec);
+        h->dev.drop(h->d_cov_ridx);
+        h->d_cov_rec = nullptr;
+        h->d_cov_ridx = nullptr;
+        h->cov_rec_cap = 0;
+        CHECK_RC(h->dev.alloc(&h->d_cov_rec, (size_t)kYRec * cap));
+        CHECK_RC(h->dev.alloc(&h->d_cov_ridx, cap + 2 * (size_t)NP + 1));
+        h->cov_rec_cap = cap;
+      }
+      int* const rcam = h->d_cov_ridx;
+      int* const rcnt = rcam + h->cov_rec_cap;
+      int* const d_rbase = rcnt + NP;
+      HIP_OK(hipMemcpyAsync(d_rbase, rbase.data(), sizeof(int) * ((size_t)NP + 1), hipMemcpyHostToDevice, s));
+      launch_cov_points_z(s, v, h->NE > 0, h->d_points, h->d_camtab, h->d_L, h->d_sz, h->d_intr_meta, h->d_Yrec, h->d_Y,
+                          h->d_cov_idx, h->d_cov_idx + std::max(1, h->NE), d_rbase, h->d_cov_rec, rcam, rcnt, S_, ld_,
+                          h->d_cov_pts);
+      HIP_OK(hipStreamSynchronize(s));  // rbase's host copy goes out of scope
+    } else {
+      // d_Y (the step's camera-major Y planes, unused on this route) takes the merged records
+      launch_cov_points(s, v, NC > 0 && h->NE > 0, h->d_L, h->d_Yrec, h->d_Y, h->d_cov_idx,
+                        h->d_cov_idx + std::max(1, h->NE), h->d_S, h->lds, h->d_cov_pts);
+    }
   }
   HIP_OK(hipEventRecord(h->cov_ev[4], s));
   double* d_ext21 = nullptr;
-  if (want_c && (ext_cov || ext_full)) {
-    if (ext_cov) {
-      if (!h->d_cov_ext) CHECK_RC(h->dev.alloc(&h->d_cov_ext, (size_t)21 * NC));
+  if (want_c && (ext_cov || intr_cov || ext_full)) {
+    if (ext_cov || intr_cov) {
+      if (!h->d_cov_ext) CHECK_RC(h->dev.alloc(&h->d_cov_ext, (size_t)21 * (NC + kIntrFreeMax)));
       d_ext21 = h->d_cov_ext;
     }
-    launch_cov_unscale(s, NC, h->d_scale_c, h->d_S, h->lds, d_ext21);
+    if (nfi > 0) launch_cov_unscale_z(s, NC, nfi, h->d_scale_c, h->d_sz, h->d_intr_act, S_, ld_, d_ext21);
+    else launch_cov_unscale(s, NC, h->d_scale_c, h->d_S, h->lds, d_ext21);
   }
   std::vector<double> hp;
   if (point_cov && NP > 0) {
@@ -4001,15 +4115,24 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
   }
   if (ext_cov && NC > 0)
     HIP_OK(hipMemcpy(ext_cov, d_ext21, sizeof(double) * 21 * (size_t)NC, hipMemcpyDeviceToHost));
+  if (intr_cov && nfi > 0)
+    HIP_OK(hipMemcpy(intr_cov, d_ext21 + 21 * (size_t)NC, sizeof(double) * 21 * (size_t)nfi, hipMemcpyDeviceToHost));
   if (ext_full && NC > 0)
-    HIP_OK(hipMemcpy2D(ext_full, (size_t)n * sizeof(double), h->d_S, (size_t)h->lds * sizeof(double),
-                       (size_t)n * sizeof(double), (size_t)n, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy2D(ext_full, (size_t)n2 * sizeof(double), S_, (size_t)ld_ * sizeof(double),
+                       (size_t)n2 * sizeof(double), (size_t)n2, hipMemcpyDeviceToHost));
   return finish(h->cov_ev[4]);
 }
 extern "C" int dab_covariance(dab_handle* h, const dab_covariance_options* opt, double* point_cov, double* ext_cov,
                               double* ext_full, dab_covariance_info* info) {
-  const int rc = covariance_impl(h, opt, point_cov, ext_cov, ext_full, info);
+  const int rc = covariance_impl(h, opt, point_cov, ext_cov, nullptr, ext_full, info, nullptr, false);
   if (h) CHECK_RC(guard_fail(h, "dab_covariance"));
+  return rc;
+}
+extern "C" int dab_covariance_intrinsics(dab_handle* h, const dab_covariance_options* opt, double* point_cov,
+                                         double* ext_cov, double* intr_cov, double* cam_full,
+                                         dab_covariance_info* info, dab_covariance_intr_info* zinfo) {
+  const int rc = covariance_impl(h, opt, point_cov, ext_cov, intr_cov, cam_full, info, zinfo, true);
+  if (h) CHECK_RC(guard_fail(h, "dab_covariance_intrinsics"));
   return rc;
 }
 

@@ -258,6 +258,13 @@ DeepArcManager::~DeepArcManager() { clear(); }
 
 DeepArcManager::Covariance DeepArcManager::covariance(const std::vector<int>& extra_const, bool freeze_camera,
                                                       bool full) {
+  return covarianceOf(extra_const, freeze_camera, full, false);
+}
+DeepArcManager::Covariance DeepArcManager::covarianceIntrinsics(const std::vector<int>& extra_const, bool full) {
+  return covarianceOf(extra_const, false, full, true);
+}
+DeepArcManager::Covariance DeepArcManager::covarianceOf(const std::vector<int>& extra_const, bool freeze_camera,
+                                                        bool full, bool with_intr) {
   DabScene scene;
   scene.build(*this, freeze_camera);
   for (int e : extra_const) {
@@ -268,15 +275,41 @@ DeepArcManager::Covariance DeepArcManager::covariance(const std::vector<int>& ex
   dab_check(dab_set_loss(dh.h, loss_type_, loss_scale_));
   dab_check(dab_set_problem(dh.h, &scene.problem));
   dab_covariance_info info{};
-  dab_check(dab_covariance(dh.h, nullptr, nullptr, nullptr, nullptr, &info));
+  dab_covariance_intr_info zinfo{};
+  if (with_intr) {
+    const std::vector<uint8_t> groups(scene.intr_nf.size(), (uint8_t)intr_free_);
+    dab_check(dab_set_intrinsics_free(dh.h, intr_free_ ? groups.data() : nullptr));
+    dab_check(dab_covariance_intrinsics(dh.h, nullptr, nullptr, nullptr, nullptr, nullptr, &info, &zinfo));
+  } else {
+    dab_check(dab_covariance(dh.h, nullptr, nullptr, nullptr, nullptr, &info));
+  }
   Covariance out;
-  const size_t nfe = (size_t)info.num_free_ext;
+  const size_t nfe = (size_t)info.num_free_ext, nfi = (size_t)zinfo.num_free_intr;
+  out.num_free_scalars = zinfo.num_free_scalars;
   if (info.status == DAB_COV_OK) {
     out.point_cov.resize(6 * point3d_.size());
     out.ext_cov.resize(21 * nfe);
-    if (full) out.ext_full.resize(36 * nfe * nfe);
-    dab_check(dab_covariance(dh.h, nullptr, out.point_cov.data(), out.ext_cov.data(),
-                             full ? out.ext_full.data() : nullptr, &info));
+    if (with_intr) {
+      out.intr_cov.resize(21 * nfi);
+      if (full) out.cam_full.resize(36 * (nfe + nfi) * (nfe + nfi));
+      dab_check(dab_covariance_intrinsics(dh.h, nullptr, out.point_cov.data(), out.ext_cov.data(),
+                                          out.intr_cov.data(), full ? out.cam_full.data() : nullptr, &info, &zinfo));
+      // the free intrinsics in ascending index: referenced by a block, with an active scalar selected
+      std::vector<char> seen(scene.intr_nf.size(), 0);
+      for (size_t o = 0; o < scene.obs_intr.size(); ++o) seen[scene.obs_intr[o]] = 1;
+      for (size_t i = 0; i < seen.size(); ++i) {
+        const int has = 0x07 | (scene.intr_nf[i] == 2 ? 0x08 : 0) | (scene.intr_nk[i] >= 1 ? 0x10 : 0) |
+                        (scene.intr_nk[i] >= 2 ? 0x20 : 0);
+        const int sel = ((intr_free_ & DAB_INTR_CENTER) ? 0x03 : 0) | ((intr_free_ & DAB_INTR_FOCAL) ? 0x0c : 0) |
+                        ((intr_free_ & DAB_INTR_DISTORTION) ? 0x30 : 0);
+        if (seen[i] && (has & sel)) out.intr_index.push_back((int)i);
+      }
+      if (out.intr_index.size() != nfi) throw "covariance: free intrinsic count mismatch";
+    } else {
+      if (full) out.ext_full.resize(36 * nfe * nfe);
+      dab_check(dab_covariance(dh.h, nullptr, out.point_cov.data(), out.ext_cov.data(),
+                               full ? out.ext_full.data() : nullptr, &info));
+    }
     // the free extrinsics in ascending index: referenced by a block and not constant
     std::vector<char> used(scene.ext_const.size(), 0);
     for (size_t o = 0; o < scene.obs_ext0.size(); ++o) {

@@ -84,8 +84,18 @@ class DeepArcManager {
     std::vector<int> ext_index;     // per row of ext_cov: index in extrinsics()
     std::vector<char> ext_kind;     // 'a' arc (or a plain extrinsic in non-shared mode) | 'r' ring
     std::vector<int> ext_position;  // arc or ring position of that extrinsic
+    // covarianceIntrinsics only
+    int num_free_scalars = 0;       // active intrinsic scalars (counted in num_parameters)
+    std::vector<double> intr_cov;   // [free intrinsics][21] upper-packed, slots cx cy f0 f1 k0 k1
+    std::vector<int> intr_index;    // per row of intr_cov: index in intrinsics()
+    std::vector<double> cam_full;   // [6 nfe + 6 nfi] square when asked for: extrinsics, then intrinsics
   };
   Covariance covariance(const std::vector<int>& extra_const = {}, bool freeze_camera = false, bool full = false);
+  // The same with the intrinsic groups of setIntrinsicsFree as unknowns (dab_covariance_intrinsics
+  // in dab.h), under this manager's loss: covariance() would report them as exactly known and
+  // understate every other variance. Inactive slots have zero rows and columns in intr_cov and
+  // cam_full. With no group set it is covariance(extra_const, false, full), cam_full = ext_full.
+  Covariance covarianceIntrinsics(const std::vector<int>& extra_const = {}, bool full = false);
 
  private:
   std::unique_ptr<DabSession> session_;
@@ -103,6 +113,7 @@ class DeepArcManager {
   std::vector<Point3d*> point3d_;
 
   void clear();
+  Covariance covarianceOf(const std::vector<int>& extra_const, bool freeze_camera, bool full, bool with_intr);
   static int ringExtrinsicIndex(int ring_position, int arc_size) {
     return ring_position == 0 ? 0 : ring_position + arc_size - 1;
   }

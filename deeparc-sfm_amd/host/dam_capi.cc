@@ -183,6 +183,44 @@ int dam_covariance(dam_manager* m, const int32_t* extra_const, int32_t n_extra, 
   });
 }
 
+int dam_covariance_intrinsics(dam_manager* m, const int32_t* extra_const, int32_t n_extra, double* point_cov,
+                              double* ext_cov, double* intr_cov, double* cam_full, int32_t* ext_label,
+                              int32_t* intr_index, dab_covariance_info* info, dab_covariance_intr_info* zinfo) {
+  return guarded([&] {
+    if (!m) throw "null manager";
+    std::vector<int> extra(extra_const, extra_const + (extra_const ? n_extra : 0));
+    const DeepArcManager::Covariance c = m->m.covarianceIntrinsics(extra, cam_full != nullptr);
+    if (info) {
+      *info = dab_covariance_info{};
+      info->status = c.status;
+      info->num_free_ext = c.ok ? (int32_t)c.ext_index.size() : 0;
+      info->first_deficient_point = c.first_deficient_point;
+      info->deficient_points = c.deficient_points;
+      info->point_pivot_ratio_min = c.point_pivot_ratio_min;
+      info->camera_pivot_ratio = c.camera_pivot_ratio;
+      info->cost = c.cost;
+      info->num_residuals = c.num_residuals;
+      info->num_parameters = c.num_parameters;
+    }
+    if (zinfo) {
+      *zinfo = dab_covariance_intr_info{};
+      zinfo->num_free_intr = c.ok ? (int32_t)c.intr_index.size() : 0;
+      zinfo->num_free_scalars = c.num_free_scalars;
+    }
+    if (!c.ok) return;
+    if (point_cov) std::memcpy(point_cov, c.point_cov.data(), c.point_cov.size() * sizeof(double));
+    if (ext_cov) std::memcpy(ext_cov, c.ext_cov.data(), c.ext_cov.size() * sizeof(double));
+    if (intr_cov) std::memcpy(intr_cov, c.intr_cov.data(), c.intr_cov.size() * sizeof(double));
+    if (cam_full) std::memcpy(cam_full, c.cam_full.data(), c.cam_full.size() * sizeof(double));
+    for (size_t i = 0; ext_label && i < c.ext_index.size(); ++i) {
+      ext_label[3 * i] = c.ext_index[i];
+      ext_label[3 * i + 1] = c.ext_kind[i] == 'r' ? 1 : 0;
+      ext_label[3 * i + 2] = c.ext_position[i];
+    }
+    for (size_t i = 0; intr_index && i < c.intr_index.size(); ++i) intr_index[i] = c.intr_index[i];
+  });
+}
+
 int dam_filter(dam_manager* m, double error_boundary, const double center[3], double radius) {
   return guarded([&] {
     double c[3] = {center[0], center[1], center[2]};

@@ -48,6 +48,9 @@ SIGNATURES = {
     "dam_set_intrinsics_free": (C.c_int, [C.c_void_p, C.c_int32]),
     "dam_covariance": (C.c_int, [C.c_void_p, _ip, C.c_int32, C.c_int32, _dp, _dp, _dp, _ip,
                                  C.POINTER(_abi.DabCovarianceInfo)]),
+    "dam_covariance_intrinsics": (C.c_int, [C.c_void_p, _ip, C.c_int32, _dp, _dp, _dp, _dp, _ip, _ip,
+                                            C.POINTER(_abi.DabCovarianceInfo),
+                                            C.POINTER(_abi.DabCovarianceIntrInfo)]),
     "dam_filter": (C.c_int, [C.c_void_p, C.c_double, _dp, C.c_double]),
     "dam_camera_centers": (C.c_int, [C.c_void_p, _dp, C.c_int32, _ip]),
     "dam_fit_hemisphere": (C.c_int, [_dp, C.c_int32, _dp, _dp, C.c_int32]),
@@ -179,6 +182,34 @@ class DeepArcManager:
         call(_p(pc, C.c_double), _p(ec, C.c_double), _p(ef, C.c_double) if full else None, _p(lab, C.c_int32))
         return dict(info=d, point_cov=_unpack_sym(pc, 3), ext_cov=_unpack_sym(ec, 6), ext_index=lab[:, 0].copy(),
                     ext_label=[("ring" if k else "arc", int(p)) for _, k, p in lab], ext_full=ef)
+
+    def covariance_intrinsics(self, extra_const=(), full=False):
+        """DeepArcManager::covarianceIntrinsics (dam_covariance_intrinsics): covariance() with the
+        groups of set_intrinsics_free as unknowns, shaped like core.Solver.covariance(intrinsics=
+        True): also `intr_cov` (nfi, 6, 6), `intr_index` and `cam_full` when full."""
+        from .core import _unpack_sym
+        ex = np.ascontiguousarray(list(extra_const), np.int32)
+        info, zinfo = _abi.DabCovarianceInfo(), _abi.DabCovarianceIntrInfo()
+
+        def call(pc, ec, zc, cf, lab, zi):
+            _check(self.lib.dam_covariance_intrinsics(self.h, _p(ex, C.c_int32) if ex.size else None, int(ex.size),
+                                                      pc, ec, zc, cf, lab, zi, C.byref(info), C.byref(zinfo)))
+        call(None, None, None, None, None, None)
+        d = {k: getattr(info, k) for k, _ in _abi.DabCovarianceInfo._fields_}
+        d.update(num_free_intr=zinfo.num_free_intr, num_free_scalars=zinfo.num_free_scalars)
+        d["status"] = _abi.COV_STATUS.get(info.status, str(info.status))
+        if info.status != 0:
+            return dict(info=d, point_cov=None, ext_cov=None, ext_index=None, ext_label=None, intr_cov=None,
+                        intr_index=None, cam_full=None)
+        nfe, nfi, npts = info.num_free_ext, zinfo.num_free_intr, self.sizes()["points"]
+        pc, ec, zc = np.zeros((npts, 6)), np.zeros((nfe, 21)), np.zeros((nfi, 21))
+        cf = np.zeros((6 * nfe + 6 * nfi, 6 * nfe + 6 * nfi)) if full else None
+        lab, zi = np.zeros((nfe, 3), np.int32), np.zeros(nfi, np.int32)
+        call(_p(pc, C.c_double), _p(ec, C.c_double), _p(zc, C.c_double), _p(cf, C.c_double) if full else None,
+             _p(lab, C.c_int32), _p(zi, C.c_int32))
+        return dict(info=d, point_cov=_unpack_sym(pc, 3), ext_cov=_unpack_sym(ec, 6), ext_index=lab[:, 0].copy(),
+                    ext_label=[("ring" if k else "arc", int(p)) for _, k, p in lab], intr_cov=_unpack_sym(zc, 6),
+                    intr_index=zi, cam_full=cf)
 
     def filterPoint3d(self, error_boundary, hemisphere_center, hemisphere_radius):  # noqa: N802
         c = np.ascontiguousarray(hemisphere_center, np.float64)

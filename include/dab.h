@@ -308,7 +308,7 @@ int dab_get_parameters(dab_handle* h, double* points, double* ext);
  * DAB_E_UNSUPPORTED for IMPLICIT_SCHUR_PCG (requested or chosen by AUTO), for more than 16 free
  * intrinsics, and for a problem without a free extrinsic (unless freeze_camera is set);
  * dab_covariance with a non-empty free set returns DAB_E_UNSUPPORTED (it would report the
- * intrinsics as exactly known). DAB_E_INVALID for a null handle (checked before any device
+ * intrinsics as exactly known; dab_covariance_intrinsics covers them). DAB_E_INVALID for a null handle (checked before any device
  * use), a null array where one is required, or group bits above 7; DAB_E_STATE before
  * dab_set_problem. */
 #define DAB_INTR_CENTER     1   /* cx, cy                      block [1], sfm.cc:60 */
@@ -415,6 +415,54 @@ typedef struct dab_covariance_info {
 
 int dab_covariance(dab_handle* h, const dab_covariance_options* opt /* NULL = defaults */,
                    double* point_cov, double* ext_cov, double* ext_full, dab_covariance_info* info);
+
+/* ---- covariance with free intrinsics ------------------------------------------------------
+ * dab_covariance refuses a handle with a non-empty free set (dab_set_intrinsics_free): treating
+ * the intrinsics as exactly known understates every other variance. This call is the same
+ * contract over one more parameter group: Sigma = (J^T J)^-1 over the referenced points, the
+ * free extrinsics and the active intrinsic scalars (those dab_solve counts in num_parameters,
+ * which info->num_parameters includes here), undamped, no sigma^2 factor, rows scaled by
+ * sqrt(rho') under a loss, all fp64, jacobi_scaling honoured.
+ *   point_cov, ext_cov  as dab_covariance
+ *   intr_cov [nfi][21]  upper-packed 6x6 per free intrinsic, ascending intrinsic index, slots
+ *                       (cx, cy, f0, f1, k0, k1)
+ *   cam_full [n'][n']   row-major, n' = 6 nfe + 6 nfi: extrinsics first, then intrinsics; both
+ *                       triangles, bitwise symmetric, its diagonal 6x6 blocks equal ext_cov and
+ *                       intr_cov bitwise
+ * Slots a model lacks or the mask leaves out are known exactly: their rows and columns in
+ * intr_cov and cam_full are exactly 0. Every array may be NULL; with all NULL the call is the
+ * size and rank query (zinfo: num_free_intr, num_free_scalars). With an empty free set (mask
+ * never set, all zero, or freeze_camera) every array and info are bitwise dab_covariance's:
+ * intr_cov is empty and cam_full is ext_full.
+ *
+ * Route: the exact step's bordered system S' of n' rows ("Covariance with free
+ * intrinsics") built as one undamped LM step builds it, its Cholesky factor, C' = S'^-1 from the
+ * factor (a second n' x n' buffer, lazy, DAB_E_NOMEM when it cannot be had, freed by
+ * dab_set_problem and dab_destroy), and the point fold-back over the cameras and the free
+ * intrinsics each point sees. zinfo->border_ms is the device time of the z rows of S'.
+ *
+ * Rank test: dab_covariance's, on the factor of the n' system: the camera test takes min / max of
+ * the squared diagonal over the rows of extrinsics and of active intrinsic scalars (the unit rows
+ * of inactive slots are left out). Return value, camera_pivot_ratio and "no array is written on
+ * a failure" as there.
+ *
+ * Refusals, state unchanged: DAB_E_UNSUPPORTED for more than 16 free intrinsics and for a
+ * non-empty free set without a free extrinsic (dab_solve's rule and wording); DAB_E_INVALID and
+ * DAB_E_STATE as dab_covariance. The handle's parameters, intrinsics, mask, loss and problem
+ * are untouched, a dab_solve after the call walks bitwise the trajectory it would have walked
+ * without it, and two calls in a row give bitwise equal arrays. Collective on a multi-rank
+ * handle: the border sums are all-reduced as in the step, every rank gets identical ext_cov,
+ * intr_cov and cam_full and its own shard's points. */
+typedef struct dab_covariance_intr_info {
+  int32_t num_free_intr;     /* free intrinsics (the set dab_solve would use) */
+  int32_t num_free_scalars;  /* their active scalars */
+  double border_ms;          /* device time of the z rows of S' (HIP events) */
+  double reserved;
+} dab_covariance_intr_info;
+
+int dab_covariance_intrinsics(dab_handle* h, const dab_covariance_options* opt /* NULL = defaults */,
+                              double* point_cov, double* ext_cov, double* intr_cov, double* cam_full,
+                              dab_covariance_info* info, dab_covariance_intr_info* zinfo);
 
 /* Dense SPD solve A x = b on the handle's device with the library's blocked Cholesky (the
  * reduced-camera-system factorisation of DAB_LINEAR_SOLVER_EXPLICIT_SCHUR; Eigen LLT in

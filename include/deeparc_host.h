@@ -14,6 +14,7 @@
  *   dam_fit_hemisphere                     the HemisphereRadius fit, sfm.cc:83-101
  *   dam_run_pipeline                       main(), sfm.cc:79-129
  *   dam_covariance                         (no reference call: ceres::Covariance after Solve)
+ *   dam_covariance_intrinsics              (the same with the free intrinsic groups as unknowns)
  * Return 0 on success, negative on error (message in dam_last_error; the C++ API throws
  * const char* like the reference).
  */
@@ -69,6 +70,13 @@ int dam_set_intrinsics_free(dam_manager* m, int32_t groups);
 int dam_covariance(dam_manager* m, const int32_t* extra_const, int32_t n_extra, int32_t freeze_camera,
                    double* point_cov, double* ext_cov, double* ext_full, int32_t* ext_label,
                    dab_covariance_info* info);
+/* DeepArcManager::covarianceIntrinsics: dab_covariance_intrinsics (dab.h) of the same scene with
+ * the groups of dam_set_intrinsics_free as unknowns. As dam_covariance (no freeze_camera), plus
+ * intr_cov [nfi][21], intr_index [nfi] (index in the intrinsic list) and cam_full [n'][n'], n' =
+ * 6 nfe + 6 nfi; query info->num_free_ext and zinfo->num_free_intr first. */
+int dam_covariance_intrinsics(dam_manager* m, const int32_t* extra_const, int32_t n_extra, double* point_cov,
+                              double* ext_cov, double* intr_cov, double* cam_full, int32_t* ext_label,
+                              int32_t* intr_index, dab_covariance_info* info, dab_covariance_intr_info* zinfo);
 int dam_filter(dam_manager* m, double error_boundary, const double center[3], double radius);
 /* out [capacity][3]; *count = number of centres (may exceed capacity) */
 int dam_camera_centers(dam_manager* m, double* out, int32_t capacity, int32_t* count);

@@ -15,7 +15,8 @@ step only: pair it with --solvers explicit).
 camera system that is not a small one), refuses a non-empty free set on every rank.
 --covariance checks dab_covariance instead: every rank calls it on its shard after the solve, and
 rank 0 compares the camera arrays across the ranks (bitwise) and, with every owner's point rows,
-against a single handle at the same parameters.
+against a single handle at the same parameters. --cov-intrinsics K does the same for
+dab_covariance_intrinsics with the first K intrinsics free.
 """
 import argparse
 import json
@@ -70,6 +71,10 @@ def main():
                     "owner's point rows, within --cov-tol of a single handle at the same parameters")
     ap.add_argument("--cov-tol", type=float, default=1e-9,
                     help="--covariance: bound on max |difference| / max |Sigma| against the single handle")
+    ap.add_argument("--cov-intrinsics", type=int, default=0,
+                    help="--covariance: the first K intrinsics are free (all groups, the same mask on every "
+                    "handle) and the call is dab_covariance_intrinsics; the camera arrays compared are then "
+                    "cam_full and the extrinsic blocks followed by the intrinsic ones")
     a = ap.parse_args()
     loss = None
     if a.loss:
@@ -157,6 +162,20 @@ def main():
         return
 
     if a.covariance:
+        def covariance_of(solver):
+            """dab_covariance, or with --cov-intrinsics dab_covariance_intrinsics under the names of the former"""
+            if a.cov_intrinsics <= 0:
+                return solver.covariance(full=True)
+            g = np.zeros(solver.problem.intr.shape[0], np.uint8)
+            g[:a.cov_intrinsics] = 7
+            solver.set_intrinsics_free(g)
+            c = solver.covariance(full=True, intrinsics=True)
+            c["info"]["num_free_ext"] += c["info"]["num_free_intr"]
+            if c["info"]["status"] == "OK":
+                c["ext_full"] = c["cam_full"]
+                c["ext_cov"] = np.concatenate([c["ext_cov"], c["intr_cov"]])
+            return c
+
         if a.config:
             glob = pkg.synth(**pkg.CONFIGS[a.config])
         else:  # 40 cameras, two of them constant: the scale gauge is fixed, J has full rank
@@ -170,7 +189,7 @@ def main():
         s.set_problem(mine)
         if a.iters > 0:
             s.solve(pkg.options(max_num_iterations=a.iters, linear_solver_type=pkg.DAB_LINEAR_SOLVER_EXPLICIT_SCHUR))
-        cov = s.covariance(full=True)
+        cov = covariance_of(s)
         s.close()
         ok_here = cov["info"]["status"] == "OK"
         status = torch.tensor([1 if ok_here else 0], dtype=torch.int32)
@@ -198,7 +217,7 @@ def main():
             if loss:
                 s1.set_loss(*loss)
             s1.set_problem(g1)
-            c1 = s1.covariance(full=True)
+            c1 = covariance_of(s1)
             s1.close()
             res = dict(ranks_ok=int(status.item()), single=c1["info"]["status"],
                        ranks_equal=bool(torch.equal(hi, lo) and torch.equal(bhi, blo)))
