@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "dab_handle.h"
 #include "dab_kernels.h"
 
 namespace dab {
@@ -459,3 +460,282 @@ void launch_cov_unscale(hipStream_t s, int NC, const double* scale_c, double* C,
 }
 
 }  // namespace dab
+
+using namespace dab;
+
+// ------------------------------------------------------------------------------------
+// dab_covariance: Sigma = (J^T J)^-1 at the current parameters, by the exact Schur route
+// ------------------------------------------------------------------------------------
+// In the solver's scaled variables (s = the Jacobi scaling dab_solve would use here), with
+// PU_p = s_p L_p^-T, Y_e = (s_c ∘ Jc^T Jp) PU_p and C = (scaled S)^-1:
+//   Sigma_cc' = s_c C_cc' s_c',  Sigma_pp = PU_p (I + sum_{e,e'} Y_e^T C_c(e)c(e') Y_e') PU_p^T.
+// The LM kernels run unchanged with radius = +inf: their sqrt(clamp(d) / radius) is exactly 0.
+//
+// with_intr (dab_covariance_intrinsics): the free intrinsics of the handle's mask join the camera
+// system as in the exact step, S' of n' = 6 NC + 6 nfi rows in the handle's z buffer with the
+// border rows of one undamped LM step; C' = S'^-1, s = (s_c, s_z), and a point's fold-back gains
+// one record Gz_p,i per free intrinsic it sees (k_cov_gz). With nfi = 0 every launch and buffer
+// is dab_covariance's. ext_full: [n'][n'] then, intr_cov [nfi][21].
+static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, double* point_cov, double* ext_cov,
+                           double* intr_cov, double* ext_full, dab_covariance_info* info,
+                           dab_covariance_intr_info* zinfo, bool with_intr) {
+  if (!with_intr && h && h->have_problem && intr_mask_any(h)) {
+    // free intrinsics are not part of the covariance: it would report them as exactly known
+    int nfi_cov = 0;
+    HIP_OK(hipSetDevice(h->device));
+    CHECK_RC(intr_free_set(h, true, &nfi_cov));
+    if (nfi_cov > 0)
+      return set_error(DAB_E_UNSUPPORTED,
+                       "dab_covariance with free intrinsics is not supported (dab_covariance_intrinsics is)");
+  }
+  clear_error();
+  if (!h) return set_error(DAB_E_INVALID, "null handle");
+  dab_covariance_options opt;
+  if (opt_in) opt = *opt_in;
+  else dab_covariance_options_init(&opt);
+  if (!(std::isfinite(opt.min_pivot_ratio) && opt.min_pivot_ratio > 0.0))
+    return set_error(DAB_E_INVALID, "min_pivot_ratio must be finite and > 0");
+  if (!info && !point_cov && !ext_cov && !intr_cov && !ext_full)
+    return set_error(DAB_E_INVALID, "null info and null arrays");
+  if (!h->have_problem) return set_error(DAB_E_STATE, "no problem set");
+  HIP_OK(hipSetDevice(h->device));
+  // free intrinsics: dab_solve's rule and refusals, before anything on the handle changes
+  CamSystem cs;
+  if (with_intr) CHECK_RC(cam_system_free_set(h, nullptr, &cs));
+  hipStream_t s = h->stream;
+  const DevView& v = h->view;
+  const int NP = h->NP, NC = h->NC;
+  if (NC > 0) CHECK_RC(build_schur_tables(h));
+  CHECK_RC(cam_system_buffers(h, true, &cs));
+  const int nfi = cs.nfi, n = cs.n, n2 = cs.n2, ld_ = cs.ld;
+  double* const S_ = cs.S;
+  dab_covariance_intr_info zout{};
+  zout.num_free_intr = nfi;
+  zout.num_free_scalars = cs.nz_scal;
+  dab_covariance_info out{};
+  out.status = DAB_COV_OK;
+  out.num_free_ext = NC;
+  out.num_free_points = NP;
+  out.first_deficient_point = -1;
+  out.schur_assembly = h->schur_tiles ? DAB_SCHUR_TILES : DAB_SCHUR_PAIRS;
+  out.num_residuals = 2 * h->N;
+  out.num_parameters = 3 * NP + 6 * NC + cs.nz_scal;
+  out.point_pivot_ratio_min = out.camera_pivot_ratio = std::numeric_limits<double>::quiet_NaN();
+  for (hipEvent_t& e : h->cov_ev)
+    if (!e) HIP_OK(hipEventCreate(&e));
+  if (nfi > 0)
+    for (hipEvent_t& e : h->cov_ev_z)
+      if (!e) HIP_OK(hipEventCreate(&e));
+  const int rgrid = cov_rank_grid(NP);
+  if (!h->lz.d_cov_stat) CHECK_RC(h->dev.alloc(&h->lz.d_cov_stat, (size_t)8 + 2 * (size_t)rgrid));
+  double* d_stat = h->lz.d_cov_stat;         // [0] deficient points, [4..6] diagonal min / max / bad
+  double* d_rpart = h->lz.d_cov_stat + 8;    // the rank kernel's work-group partials
+
+  // ---- undamped linearisation at the current parameters ----
+  HIP_OK(hipMemsetAsync(h->d_scal + S_XERR, 0, sizeof(double), s));
+  HIP_OK(hipEventRecord(h->cov_ev[0], s));
+  CHECK_RC(eval_jacobian_and_blocks(h, false));
+  if (nfi > 0) CHECK_RC(intr_eval(h));
+  launch_jacobi_scale(h, nfi, opt.jacobi_scaling);
+  HIP_OK(hipEventRecord(h->cov_ev[1], s));
+  CHECK_RC(read_scalars(h));
+  if (h->h_scal[S_COST_BAD] != 0.0)
+    return set_error(DAB_E_INVALID, "residuals are not finite at the current parameters");
+  const double x_cost = 0.5 * h->h_scal[S_COST];
+  out.cost = x_cost;
+
+  // ---- point factor without LM diagonal, and the point-side rank test ----
+  dab_options lm;
+  dab_options_init(&lm);
+  const StepScalars sc{std::numeric_limits<double>::infinity(), lm.min_lm_diagonal, lm.max_lm_diagonal};
+  HIP_OK(hipMemsetAsync(h->d_flags, 0, sizeof(int) * 4, s));
+  launch_point_factor(s, v, h->d_V, h->d_g, h->d_scale_p, sc, h->d_L, h->d_q, h->d_flags);
+  double* d_ratio = h->d_dp;  // [NP] of the step buffer (scratch between LM steps)
+  launch_cov_point_rank(s, NP, h->d_V, h->d_scale_p, opt.min_pivot_ratio, d_ratio, d_rpart, rgrid);
+  launch_final_sum(s, rgrid, 1, d_rpart, d_stat);
+  CHECK_RC(h->allreduce(d_stat, 1, ncclMax));  // every rank takes the same exit
+  double hstat[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  std::vector<double> hmin((size_t)rgrid);
+  HIP_OK(hipMemcpyAsync(hstat, d_stat, sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(hmin.data(), d_rpart + rgrid, sizeof(double) * (size_t)rgrid, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  CHECK_RC(p2p_check(h->p2p_main));
+  if (NP > 0) out.point_pivot_ratio_min = *std::min_element(hmin.begin(), hmin.end());
+  auto finish = [&](hipEvent_t last) -> int {
+    float ms = 0.f;
+    HIP_OK(hipEventSynchronize(last));
+    HIP_OK(hipEventElapsedTime(&ms, h->cov_ev[0], h->cov_ev[1]));
+    out.evaluate_ms = ms;
+    if (last != h->cov_ev[1]) {
+      HIP_OK(hipEventElapsedTime(&ms, h->cov_ev[1], h->cov_ev[2]));
+      out.factor_ms = ms;
+    }
+    if (last == h->cov_ev[4]) {
+      HIP_OK(hipEventElapsedTime(&ms, h->cov_ev[2], h->cov_ev[3]));
+      out.inverse_ms = ms;
+      HIP_OK(hipEventElapsedTime(&ms, h->cov_ev[3], h->cov_ev[4]));
+      out.points_ms = ms;
+    }
+    if (nfi > 0 && last != h->cov_ev[1]) {
+      HIP_OK(hipEventElapsedTime(&ms, h->cov_ev_z[0], h->cov_ev_z[1]));
+      zout.border_ms = ms;
+    }
+    if (info) *info = out;
+    if (zinfo) *zinfo = zout;
+    return 0;
+  };
+  if (hstat[0] > 0.0) {
+    out.status = DAB_COV_RANK_DEFICIENT;
+    out.deficient_points = (int)hstat[0];
+    std::vector<double> ratio((size_t)NP);
+    if (NP > 0) HIP_OK(hipMemcpy(ratio.data(), d_ratio, sizeof(double) * (size_t)NP, hipMemcpyDeviceToHost));
+    int first = -1;
+    for (int i = 0; i < NP; ++i)
+      if (!(ratio[i] > opt.min_pivot_ratio) && (first < 0 || h->pt_of[i] < first)) first = h->pt_of[i];
+    out.first_deficient_point = first;
+    return finish(h->cov_ev[1]);
+  }
+
+  // ---- S and its factor (the exact step's assembly) ----
+  if (NC > 0) {
+    CHECK_RC(cam_system_assemble(h, cs, sc, x_cost, false));
+    if (h->schur_tiles) {
+      // the point kernel reads per-entry records: the tile path keeps per-(point, camera) sums only
+      if (!h->lz.d_Yrec) CHECK_RC(h->dev.alloc(&h->lz.d_Yrec, (size_t)kYRec * std::max(1, h->NE)));
+      if (point_cov)
+        launch_entry_y(s, v, h->d_points, h->d_camtab, h->d_scale_c, h->d_L, YBufs{h->d_Y, h->d_Yp, false}, false,
+                       h->lz.d_Yrec);
+    }
+    if (nfi > 0) {
+      HIP_OK(hipEventRecord(h->cov_ev_z[0], s));
+      CHECK_RC(intr_border_rows(h, nfi, sc, S_, ld_));
+      HIP_OK(hipEventRecord(h->cov_ev_z[1], s));
+    }
+    if (chol_factor_solve(h->chol, s, n2, S_, ld_, cs.yc, h->d_flags + 1) != 0)
+      return set_error(DAB_E_DEVICE, "dense Cholesky launch failed");
+    if (nfi > 0) launch_cov_diag_minmax_act(s, n2, n, h->lz.d_intr_act, chol_diag_blocks(h->chol), d_stat + 4);
+    else launch_cov_diag_minmax(s, n, chol_diag_blocks(h->chol), d_stat + 4);
+  }
+  HIP_OK(hipEventRecord(h->cov_ev[2], s));
+  HIP_OK(hipMemcpyAsync(hstat + 4, d_stat + 4, sizeof(double) * 3, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(h->h_flags, h->d_flags, sizeof(int) * 4, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  CHECK_RC(p2p_check(h->p2p_main));
+  if (h->h_flags[0] != 0) return set_error(DAB_E_DEVICE, "point factor failed after the rank test passed");
+  if (NC > 0) {
+    if (h->h_flags[1] & 2)
+      return set_error(DAB_E_DEVICE, "dense Cholesky: a bounded wait between work-groups timed out");
+    const bool flagged = h->h_flags[1] != 0 || hstat[6] != 0.0;
+    out.camera_pivot_ratio = flagged ? 0.0 : hstat[4] / hstat[5];
+    if (!(out.camera_pivot_ratio > opt.min_pivot_ratio)) {
+      out.status = DAB_COV_RANK_DEFICIENT;
+      return finish(h->cov_ev[2]);
+    }
+  }
+  if (!point_cov && !ext_cov && !intr_cov && !ext_full) return finish(h->cov_ev[2]);  // the size / rank query
+
+  // ---- C = S^-1 from the factor, the point blocks, the unscaled camera part ----
+  const bool want_c = NC > 0 && (point_cov || ext_cov || intr_cov || ext_full);
+  if (want_c && nfi > 0) {
+    // the second n' x n' buffer (n' changes with the free set: kept while it fits)
+    const size_t need = (size_t)n2 * ld_;
+    if (need > h->lz.covZz_cap) {
+      h->dev.drop(h->lz.d_covZz);
+      h->lz.d_covZz = nullptr;
+      h->lz.covZz_cap = 0;
+      CHECK_RC(h->dev.alloc(&h->lz.d_covZz, need));
+      h->lz.covZz_cap = need;
+    }
+    launch_cov_inverse(s, n2, S_, ld_, chol_diag_blocks(h->chol), h->lz.d_covZz, ld_, S_, ld_);
+  } else if (want_c) {
+    if (!h->lz.d_covZ) CHECK_RC(h->dev.alloc(&h->lz.d_covZ, (size_t)n * h->lds));
+    launch_cov_inverse(s, n, h->d_S, h->lds, chol_diag_blocks(h->chol), h->lz.d_covZ, h->lds, h->d_S, h->lds);
+  }
+  HIP_OK(hipEventRecord(h->cov_ev[3], s));
+  if (point_cov) {
+    if (!h->lz.d_cov_pts) CHECK_RC(h->dev.alloc(&h->lz.d_cov_pts, (size_t)6 * std::max(1, NP)));
+    if (!h->lz.d_cov_idx) CHECK_RC(h->dev.alloc(&h->lz.d_cov_idx, (size_t)std::max(1, h->NE) + (size_t)std::max(1, NP)));
+    if (nfi > 0) {
+      // where each point's records begin: its entries, then the free intrinsics it sees
+      std::vector<int> ptmask((size_t)std::max(1, NP)), ent_ptr((size_t)NP + 1), rbase((size_t)NP + 1);
+      HIP_OK(hipMemcpyAsync(ptmask.data(), h->lz.d_ptmask, sizeof(int) * (size_t)NP, hipMemcpyDeviceToHost, s));
+      HIP_OK(hipMemcpyAsync(ent_ptr.data(), h->d_pt_ent_ptr, sizeof(int) * ((size_t)NP + 1), hipMemcpyDeviceToHost, s));
+      HIP_OK(hipStreamSynchronize(s));
+      long long nz_rec = 0;
+      for (int p = 0; p < NP; ++p) {
+        rbase[(size_t)p] = (int)(ent_ptr[(size_t)p] + nz_rec);
+        nz_rec += __builtin_popcount((unsigned)ptmask[(size_t)p]);
+      }
+      const long long total = (long long)ent_ptr[(size_t)NP] + nz_rec;
+      if (total > INT_MAX) return set_error(DAB_E_UNSUPPORTED, "too many fold-back records for 32-bit indices");
+      rbase[(size_t)NP] = (int)total;
+      const size_t cap = (size_t)std::max<long long>(1, total);
+      if (cap > h->lz.cov_rec_cap) {
+        h->dev.drop(h->lz.d_cov_rec);
+        h->dev.drop(h->lz.d_cov_ridx);
+        h->lz.d_cov_rec = nullptr;
+        h->lz.d_cov_ridx = nullptr;
+        h->lz.cov_rec_cap = 0;
+        CHECK_RC(h->dev.alloc(&h->lz.d_cov_rec, (size_t)kYRec * cap));
+        CHECK_RC(h->dev.alloc(&h->lz.d_cov_ridx, cap + 2 * (size_t)NP + 1));
+        h->lz.cov_rec_cap = cap;
+      }
+      int* const rcam = h->lz.d_cov_ridx;
+      int* const rcnt = rcam + h->lz.cov_rec_cap;
+      int* const d_rbase = rcnt + NP;
+      HIP_OK(hipMemcpyAsync(d_rbase, rbase.data(), sizeof(int) * ((size_t)NP + 1), hipMemcpyHostToDevice, s));
+      launch_cov_points_z(s, v, h->NE > 0, h->d_points, h->d_camtab, h->d_L, h->lz.d_sz, h->lz.d_intr_meta, h->lz.d_Yrec, h->d_Y,
+                          h->lz.d_cov_idx, h->lz.d_cov_idx + std::max(1, h->NE), d_rbase, h->lz.d_cov_rec, rcam, rcnt, S_, ld_,
+                          h->lz.d_cov_pts);
+      HIP_OK(hipStreamSynchronize(s));  // rbase's host copy goes out of scope
+    } else {
+      // d_Y (the step's camera-major Y planes, unused on this route) takes the merged records
+      launch_cov_points(s, v, NC > 0 && h->NE > 0, h->d_L, h->lz.d_Yrec, h->d_Y, h->lz.d_cov_idx,
+                        h->lz.d_cov_idx + std::max(1, h->NE), h->d_S, h->lds, h->lz.d_cov_pts);
+    }
+  }
+  HIP_OK(hipEventRecord(h->cov_ev[4], s));
+  double* d_ext21 = nullptr;
+  if (want_c && (ext_cov || intr_cov || ext_full)) {
+    if (ext_cov || intr_cov) {
+      if (!h->lz.d_cov_ext) CHECK_RC(h->dev.alloc(&h->lz.d_cov_ext, (size_t)21 * (NC + kIntrFreeMax)));
+      d_ext21 = h->lz.d_cov_ext;
+    }
+    if (nfi > 0) launch_cov_unscale_z(s, NC, nfi, h->d_scale_c, h->lz.d_sz, h->lz.d_intr_act, S_, ld_, d_ext21);
+    else launch_cov_unscale(s, NC, h->d_scale_c, h->d_S, h->lds, d_ext21);
+  }
+  std::vector<double> hp;
+  if (point_cov && NP > 0) {
+    hp.resize((size_t)6 * NP);
+    HIP_OK(hipMemcpyAsync(hp.data(), h->lz.d_cov_pts, hp.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  HIP_OK(hipStreamSynchronize(s));
+  // every array is written from here on, after the last check that can fail
+  if (point_cov) {
+    const size_t npts = (size_t)h->prob.num_points;
+    std::fill(point_cov, point_cov + 6 * npts, std::numeric_limits<double>::quiet_NaN());
+    for (int i = 0; i < NP; ++i)
+      std::memcpy(point_cov + 6 * (size_t)h->pt_of[i], hp.data() + 6 * (size_t)i, 6 * sizeof(double));
+  }
+  if (ext_cov && NC > 0)
+    HIP_OK(hipMemcpy(ext_cov, d_ext21, sizeof(double) * 21 * (size_t)NC, hipMemcpyDeviceToHost));
+  if (intr_cov && nfi > 0)
+    HIP_OK(hipMemcpy(intr_cov, d_ext21 + 21 * (size_t)NC, sizeof(double) * 21 * (size_t)nfi, hipMemcpyDeviceToHost));
+  if (ext_full && NC > 0)
+    HIP_OK(hipMemcpy2D(ext_full, (size_t)n2 * sizeof(double), S_, (size_t)ld_ * sizeof(double),
+                       (size_t)n2 * sizeof(double), (size_t)n2, hipMemcpyDeviceToHost));
+  return finish(h->cov_ev[4]);
+}
+extern "C" int dab_covariance(dab_handle* h, const dab_covariance_options* opt, double* point_cov, double* ext_cov,
+                              double* ext_full, dab_covariance_info* info) {
+  const int rc = covariance_impl(h, opt, point_cov, ext_cov, nullptr, ext_full, info, nullptr, false);
+  if (h) CHECK_RC(guard_fail(h, "dab_covariance"));
+  return rc;
+}
+extern "C" int dab_covariance_intrinsics(dab_handle* h, const dab_covariance_options* opt, double* point_cov,
+                                         double* ext_cov, double* intr_cov, double* cam_full,
+                                         dab_covariance_info* info, dab_covariance_intr_info* zinfo) {
+  const int rc = covariance_impl(h, opt, point_cov, ext_cov, intr_cov, cam_full, info, zinfo, true);
+  if (h) CHECK_RC(guard_fail(h, "dab_covariance_intrinsics"));
+  return rc;
+}

@@ -1,4 +1,5 @@
-// dab_internal.h — shared declarations of the MI355X BA library (not part of the ABI).
+// dab_internal.h — the error reporting every file of the library shares, the plain C++ ones
+// included (not part of the ABI). The handle and what its host files share: dab_handle.h.
 #pragma once
 #include <cstdint>
 #include <string>

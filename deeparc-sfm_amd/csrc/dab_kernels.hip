@@ -981,7 +981,7 @@ __global__ __launch_bounds__(1024) void k_eval_points_lds(DevView v, const doubl
 // store-wait-count-load chain of a last-arriver sum (~2.5 us at C3). Same-address atomics
 // serialize at the memory side (~12 ns each), so the adds are spread over kFxCopies
 // shards of their own lines (8 work-groups per shard at C3). Readers sum the shards and
-// convert: cost = hi + lo * 2^-52 (dab_solver.hip, read_scalars). Two shard sets alternate
+// convert: cost = hi + lo * 2^-52 (dab_solver.hip: read_scalars). Two shard sets alternate
 // between consecutive passes: block 0 of a pass zeroes the set the next pass adds into
 // (fx_next), so no memset or extra launch runs in front of the kernel; the set of a pass
 // stays valid until the pass after next.

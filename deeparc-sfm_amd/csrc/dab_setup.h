@@ -5,7 +5,7 @@
 // rig's composed observations) are built on the GPU from the caller's arrays: rocPRIM
 // radix sorts (stable, so every order is the host counting sort's), scans and
 // gather / scatter passes. The results are bitwise those of the host passes in
-// dab_solver.hip (kept as the reference path, DAB_SETUP_HOST=1).
+// dab_problem.hip (kept as the reference path, DAB_SETUP_HOST=1).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,6 +1,6 @@
 // dab_setup.hip — dab_set_problem's orderings and reduction tables built on the GPU.
 //
-// The host passes of dab_solver.hip (the reference path, DAB_SETUP_HOST=1) are stable
+// The host passes of dab_problem.hip (the reference path, DAB_SETUP_HOST=1) are stable
 // counting sorts and gathers over every observation; at BASELINE config 5 (10M
 // observations) they took ~0.7 s per set-up, and the reference's sfm.cc loop re-runs the
 // set-up after every filterPoint3d round (sfm.cc:118-127). Here the same orders come from

@@ -182,3 +182,68 @@ def test_release_caches_between_handles(pkg, gpu):
         assert other[0] == ref[0]
         np.testing.assert_array_equal(other[2], ref[2])
         np.testing.assert_array_equal(other[3], ref[3])
+
+
+# what a covariance call reports besides its arrays and stage times
+_COV_INFO = ("status", "num_free_ext", "num_free_points", "first_deficient_point", "deficient_points",
+             "schur_assembly", "point_pivot_ratio_min", "camera_pivot_ratio", "cost", "num_residuals",
+             "num_parameters")
+_lazy_probs = {}
+
+
+def _lazy_prob(pkg, name):
+    """A cov_ref problem, built once and never modified (every call below works on a copy)."""
+    import cov_ref
+    if name not in _lazy_probs:
+        _lazy_probs[name] = getattr(cov_ref, name)(pkg)
+    return _lazy_probs[name]
+
+
+def _lazy_call(pkg, s, prob, call):
+    """set_problem(copy of prob), then the call; everything it returns, as a list of arrays."""
+    p = prob.copy()
+    s.set_problem(p)
+    if call == "jacobians":
+        return list(s.jacobians())
+    if call == "solve":
+        summ = s.solve(pkg.options(max_num_iterations=3, linear_solver_type=pkg.DAB_LINEAR_SOLVER_EXPLICIT_SCHUR))
+        return [np.array([it["cost"] for it in summ["iterations"]]), p.points.copy(), p.ext.copy()]
+    if call == "cov-intr":
+        s.set_intrinsics_free(7)
+    g = s.covariance(full=True, intrinsics=call == "cov-intr")
+    assert g["info"]["status"] == "OK"
+    assert g["info"]["schur_assembly"] == (0 if call == "cov-pairs" else 1)  # pairs | tiles
+    out = [g[k] for k in sorted(g) if isinstance(g[k], np.ndarray)]
+    assert len(out) == (6 if call == "cov-intr" else 4)  # point_cov, ext_cov, ext_index, the full matrix
+    #                                                      (and intr_cov, intr_index)
+    return out + [np.array([g["info"][k] for k in _COV_INFO[1:]], np.float64)]
+
+
+@pytest.mark.parametrize("call,a,b", [("jacobians", "bal40", "bal170"), ("cov-pairs", "bal40", "bal170"),
+                                      ("cov-tiles", "rig3x5", "rig6x20"), ("cov-intr", "rig3x5", "rig6x20"),
+                                      ("solve", "bal40", "bal170"), ("solve", "rig3x5", "rig6x20")])
+def test_lazy_buffers_follow_the_problem(pkg, gpu, monkeypatch, call, a, b):
+    """The buffers a call allocates on first use (the parity Jacobians, the covariance's Z, records
+    and blocks, the free-intrinsic system, the explicit step's Y records) belong to the problem
+    they were sized for: on ONE handle, A, then the larger B (a buffer kept from A would be
+    overrun), then A again give bitwise what a fresh handle gives on B, and what A gave first."""
+    if call == "cov-pairs":
+        monkeypatch.setenv("DAB_SCHUR_TILES", "0")  # read when a handle is created
+    pa, pb = _lazy_prob(pkg, a), _lazy_prob(pkg, b)
+    assert pb.num_obs > pa.num_obs and pb.ext.shape[0] > pa.ext.shape[0]
+    fresh = pkg.Solver(0)
+    try:
+        ref_b = _lazy_call(pkg, fresh, pb, call)
+    finally:
+        fresh.close()
+    s = pkg.Solver(0)
+    try:
+        first_a = _lazy_call(pkg, s, pa, call)
+        got_b = _lazy_call(pkg, s, pb, call)
+        again_a = _lazy_call(pkg, s, pa, call)
+    finally:
+        s.close()
+    for got, ref in ((got_b, ref_b), (again_a, first_a)):
+        assert len(got) == len(ref)
+        for x, y in zip(got, ref):
+            np.testing.assert_array_equal(x, y)

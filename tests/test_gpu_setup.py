@@ -1,6 +1,6 @@
 """dab_set_problem on the device (csrc/dab_setup.hip: rocPRIM stable radix sorts, scans and
 gather passes) against the host reference path (DAB_SETUP_HOST=1, the counting sorts of
-dab_solver.hip's setup_host). The layouts decide every summation order of the solver, so
+dab_problem.hip's setup_host). The layouts decide every summation order of the solver, so
 the two paths must give bitwise-identical LM trajectories (costs, CG counts, parameters),
 residuals and filter masks on every problem shape: BAL, rig (composed observations, pair
 chunks, runs of one point on one camera), frozen cameras, unreferenced points and
