@@ -27,6 +27,7 @@
 
 #include "dab_devmem.h"
 #include "dab_kernels.h"
+#include "dab_warm.h"
 #include "dab_wave.h"
 
 namespace dab {
@@ -1377,11 +1378,6 @@ Dev* chol_mem(CholCtx* c) { return c ? &c->mem : nullptr; }
 static_assert(kCholBlk == kBlk && kCholBlkL == 1024 && NB == 64, "dab_cov.hip reads the block scratch by these");
 const double* chol_diag_blocks(CholCtx* c) { return c ? c->blk : nullptr; }
 
-// Loads this translation unit's code object on the current device now: otherwise the first
-// launch of any of its kernels pays for it (10-40 ms, inside a process's first LM iteration).
-void warm_chol() {
-  hipFuncAttributes a;
-  (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(k_panel));
-}
+DAB_WARM_TU(k_panel);
 
 }  // namespace dab

@@ -21,6 +21,8 @@
 
 #include "dab_handle.h"
 #include "dab_kernels.h"
+#include "dab_rows.h"
+#include "dab_warm.h"
 
 namespace dab {
 
@@ -399,6 +401,94 @@ __global__ __launch_bounds__(256) void k_cov_ext_blocks(int NC, const double* __
 }
 }  // namespace
 
+// dab_covariance_intrinsics: the records of a point's fold-back with free intrinsics. Thread =
+// point. Its merged camera records (k_cov_merge: slots pt_ent_ptr[p] .. of Ym / mcam, mcnt[p] of
+// them; none when with_cams is 0) move to slot rbase[p] of rec / rcam, and behind them goes one
+// record per distinct free intrinsic i the point sees, Gz_p,i = sum_{o of p with intrinsic i}
+// (s_z ∘ J_z,o)^T J_p,o PU_p (6x3, laid out as a Y record, "camera" NC + i), in first-seen
+// order of the point's SELL slots, each summed in slot order. rbase[p + 1] - rbase[p] = the
+// point's entries + the free intrinsics it sees (ptmask), so the records of a point never
+// reach the next one's. rcnt[p] = the record count.
+template <int LOSS>
+__global__ __launch_bounds__(256) void k_cov_gz(DevView v, const double* __restrict__ points,
+                                                const double* __restrict__ camtab, const double* __restrict__ PU,
+                                                const double* __restrict__ sz, const int2* __restrict__ meta,
+                                                int with_cams, const int* __restrict__ rbase,
+                                                const double* __restrict__ Ym, const int* __restrict__ mcam,
+                                                const int* __restrict__ mcnt, double* __restrict__ rec,
+                                                int* __restrict__ rcam, int* __restrict__ rcnt) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= v.NP) return;
+  const GlobalTabs tb{camtab, v.intr};
+  const LossK lk = loss_of(v);
+  const int base = rbase[p];
+  int n = 0;
+  if (with_cams) {
+    const int eb = v.pt_ent_ptr[p];
+    n = mcnt[p];
+    for (int i = 0; i < n; ++i) {
+      const double2* src = reinterpret_cast<const double2*>(Ym + (size_t)kYRec * (eb + i));
+      double2* dst = reinterpret_cast<double2*>(rec + (size_t)kYRec * (base + i));
+#pragma unroll
+      for (int k = 0; k < 9; ++k) dst[k] = src[k];
+      rcam[base + i] = mcam[eb + i];
+    }
+  }
+  const int sl = p >> 6, lane = p & 63;
+  const int off = v.slice_off[sl], len = (v.slice_off[sl + 1] - off) >> 6;
+  const double X[3] = {points[3 * (size_t)p], points[3 * (size_t)p + 1], points[3 * (size_t)p + 2]};
+  const double* pu = PU + 6 * (size_t)p;  // upper-packed 00 01 02 11 12 22
+  const double u00 = pu[0], u01 = pu[1], u02 = pu[2], u11 = pu[3], u12 = pu[4], u22 = pu[5];
+  int done = 0;
+  for (int k0 = 0; k0 < len; ++k0) {
+    const int4 lead = v.obs_idx[off + 64 * k0 + lane];
+    if (lead.x < 0) continue;  // padding slot
+    const int zi = meta[lead.w].x;
+    if (zi < 0 || ((done >> zi) & 1)) continue;
+    done |= 1 << zi;
+    double g[18];
+#pragma unroll
+    for (int t = 0; t < 18; ++t) g[t] = 0.0;
+    for (int k = k0; k < len; ++k) {
+      const int s = off + 64 * k + lane;
+      const int4 id = v.obs_idx[s];
+      if (id.x < 0) continue;
+      const int2 mt = meta[id.w];
+      if (mt.x != zi) continue;
+      const double2 xy = v.obs_xy[s];
+      double ru, rv, jx0[3], jx1[3], rho;
+      obs_rows_l<LOSS, true, -1>(lk, rho, id, xy, X, tb, ru, rv, jx0, jx1, nullptr, nullptr);
+      double P[3], Kr[6], z0[6], z1[6];
+      obs_cam_point(id, X, tb, P);
+      tb.k(id.w, Kr);
+      intr_rows<LOSS>(P, Kr, xy.x, xy.y, lk, mt.y & 63, ((mt.y >> 16) & 1) != 0, z0, z1);
+      // a_o = J_p PU_p, rows 0 and 1
+      const double a0 = jx0[0] * u00, a1 = jx0[0] * u01 + jx0[1] * u11, a2 = jx0[0] * u02 + jx0[1] * u12 + jx0[2] * u22;
+      const double b0 = jx1[0] * u00, b1 = jx1[0] * u01 + jx1[1] * u11, b2 = jx1[0] * u02 + jx1[1] * u12 + jx1[2] * u22;
+#pragma unroll
+      for (int a = 0; a < 6; ++a) {
+        const double s0 = sz[6 * zi + a] * z0[a], s1 = sz[6 * zi + a] * z1[a];
+        g[3 * a] += s0 * a0 + s1 * b0;
+        g[3 * a + 1] += s0 * a1 + s1 * b1;
+        g[3 * a + 2] += s0 * a2 + s1 * b2;
+      }
+    }
+    double2* dst = reinterpret_cast<double2*>(rec + (size_t)kYRec * (base + n));
+#pragma unroll
+    for (int k = 0; k < 9; ++k) dst[k] = make_double2(g[2 * k], g[2 * k + 1]);
+    rcam[base + n] = v.NC + zi;
+    ++n;
+  }
+  rcnt[p] = n;
+}
+void launch_cov_gz(hipStream_t s, const DevView& v, const double* points, const double* camtab, const double* PU,
+                   const double* sz, const int2* meta, bool with_cams, const int* rbase, const double* Ym,
+                   const int* mcam, const int* mcnt, double* rec, int* rcam, int* rcnt) {
+  if (v.NP <= 0) return;
+  DAB_LOSS_SWITCH(v.loss, k_cov_gz<LOSS><<<grid_for(v.NP, 256, 1 << 20), 256, 0, s>>>(
+                              v, points, camtab, PU, sz, meta, with_cams ? 1 : 0, rbase, Ym, mcam, mcnt, rec, rcam, rcnt));
+}
+
 void launch_cov_diag_minmax(hipStream_t s, int n, const double* Ld, double* out) {
   k_cov_diag_minmax<<<1, 256, 0, s>>>(n, Ld, out);
 }
@@ -458,6 +548,8 @@ void launch_cov_unscale(hipStream_t s, int NC, const double* scale_c, double* C,
   k_cov_unscale<<<(unsigned)((n * n + 255) / 256), 256, 0, s>>>((int)n, scale_c, C, ldc);
   if (ext_cov) k_cov_ext_blocks<<<(21 * NC + 255) / 256, 256, 0, s>>>(NC, C, ldc, ext_cov);
 }
+
+DAB_WARM_TU(k_cov_diag_minmax);
 
 }  // namespace dab
 

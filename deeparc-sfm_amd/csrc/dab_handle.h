@@ -638,7 +638,6 @@ int build_schur_tables(dab_handle* h);
 int build_pcg_buffers(dab_handle* h);
 
 // ---- dab_solver.hip ----
-void warm_solver();
 int eval_pass(dab_handle* h, bool camtab_ready, hipEvent_t ev_mid = nullptr, hipEvent_t ev_end = nullptr,
               hipEvent_t ev_pair0 = nullptr, hipEvent_t ev_pair1 = nullptr, bool* pair_rec = nullptr);
 int eval_jacobian_and_blocks(dab_handle* h, bool with_norms, bool tables_current = false);

@@ -5,6 +5,7 @@
 #include <mutex>
 
 #include "dab_handle.h"
+#include "dab_warm.h"
 
 using namespace dab;
 
@@ -67,6 +68,10 @@ void pinned_give(void* p, size_t bytes) {
   if (!p) return;
   std::lock_guard<std::mutex> lk(cache_mu());
   pinned_cache()[bytes].push_back(p);
+}
+WarmTable& warm_table() {
+  static WarmTable t = {};
+  return t;
 }
 }  // namespace dab
 
@@ -154,12 +159,15 @@ static int create_common(int device, dab_handle** out) {
   // kernel launch of a translation unit would otherwise pay for it mid-solve)
   static bool warmed[64] = {};
   if (device < 64 && !warmed[device]) {
-    warm_kernels();
-    warm_chol();
-    warm_pcg();
-    warm_p2p();
-    warm_setup();
-    warm_solver();
+    const WarmTable& t = warm_table();
+    if (t.n > kWarmMax) {
+      delete h;
+      return set_error(DAB_E_STATE, "code-object warm-up table full: raise kWarmMax (dab_warm.h)");
+    }
+    for (int i = 0; i < t.n; ++i) {
+      hipFuncAttributes a;
+      (void)hipFuncGetAttributes(&a, t.fn[i]);
+    }
     warmed[device] = true;
     phase("code objects");
   }

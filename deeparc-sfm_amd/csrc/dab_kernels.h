@@ -1,4 +1,6 @@
-// dab_kernels.h — launchers of the gfx950 kernels (dab_kernels.hip, dab_chol.hip).
+// dab_kernels.h — launchers of the gfx950 kernels (dab_kernels.hip, dab_k_*.hip, dab_pcg.hip,
+// dab_chol.hip, dab_cov.hip) and the constants and views they share. Device-side helpers:
+// dab_rows.h (row arithmetic, data layout), dab_reduce.h, dab_wave.h.
 #pragma once
 #include <string>
 #include <hip/hip_runtime.h>
@@ -112,6 +114,8 @@ struct ChunkLists {
   const int* gen = nullptr;  // [ngen] the others
 };
 
+// ---- evaluation passes (dab_kernels.hip; launch_eval_points, eval_points_*: dab_k_points.hip;
+// fused_eval_fits, launch_eval_bal: dab_k_fused.hip) ------------------------------------------
 // camera tables for all extrinsics from ext[E][6]
 void launch_cam_tables(hipStream_t s, int E, const double* ext, double* camtab);
 // Point side of the evaluation pass (rows a1-a4, matrix-free): residual + d r / d X per
@@ -129,6 +133,9 @@ inline bool eval_points_fx(int wps) { return wps <= -100 && (-wps - 100) / 1000 
 // whether the chosen variant reads camtab (the LDS variants build R,t from ext themselves)
 bool eval_points_needs_camtab(int wps);
 bool eval_points_lds_fits(int E);
+// extrinsics (and intrinsics) whose R,t (and K) the LDS-table passes hold: k_eval_points_lds,
+// k_eval_points_pf, k_eval_bal
+constexpr int kLdsCams = 1024;
 // Full Jacobian planes (parity API): Jfull[30][N], r[N]
 void launch_jacobian_full(hipStream_t s, const DevView& v, const double* points,
                           const double* camtab, double* r, double* Jfull);
@@ -189,7 +196,8 @@ void launch_final_sum(hipStream_t s, int grid, int K, const double* partial, dou
 void launch_cam_norms(hipStream_t s, int E, const int* ext_col, const double* ext,
                       const double* ext_c, const double* ug, double* out);
 
-// ---- per-iteration (LM step) kernels --------------------------------------------------
+// ---- per-iteration (LM step) kernels (dab_k_step.hip; launch_schur_*, schur_tile_*:
+// dab_k_tiles.hip; launch_candidate: dab_kernels.hip) ---------------------------------------
 struct StepScalars {
   double radius, min_diag, max_diag;
 };
@@ -297,7 +305,7 @@ void launch_candidate(hipStream_t s, const DevView& v, const double* points, con
 void launch_grad_points(hipStream_t s, int NP, const double* x, const double* g /*[3][NP]*/,
                         double* partial, int grid);
 
-// ---- free intrinsics in the exact Schur step (dab_set_intrinsics_free) --------------------
+// ---- free intrinsics in the exact Schur step (dab_set_intrinsics_free; dab_k_intr.hip) -----
 // meta[NI]: x = free intrinsic index or -1; y = active columns (bits 0..5: cx cy f0 f1 k0 k1
 // selected by the mask and present in the model) | columns present in the model << 8 |
 // (nf == 1) << 16. act[nfi]: the active bits by free index. zg[nfi][kIntrRec]: U_zz upper (21) |
@@ -471,11 +479,5 @@ void launch_cov_unscale_z(hipStream_t s, int NC, int nfi, const double* scale_c,
                           double* C, int ldc, double* blocks);
 
 int grid_for(int n, int block, int cap);
-
-// code-object warm-up, one per translation unit (called at handle creation)
-void warm_chol();
-void warm_kernels();
-void warm_pcg();
-void warm_p2p();
 
 }  // namespace dab

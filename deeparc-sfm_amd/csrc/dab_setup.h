@@ -100,7 +100,5 @@ void su_tile_sort(hipStream_t s, int NP, const int* pt_ent_ptr, const int* ent_c
 void su_tile_batch(hipStream_t s, int nbatch, int NC, const int* batch_pt, const int* batch_rec, const int* pt_ent_ptr,
                    const int2* sch, const int4* obs_idx, int hdr_bytes, unsigned char* hdr, int4* rec, int4* robs);
 void su_tile_hits(hipStream_t s, int NP, int nb, const int* pt_ent_ptr, const int2* sch, int* hits);
-// code-object warm-up (handle creation)
-void warm_setup();
 
 }  // namespace dab

@@ -17,7 +17,9 @@
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
 
+#include "dab_kernels.h"
 #include "dab_setup.h"
+#include "dab_warm.h"
 
 namespace dab {
 
@@ -275,10 +277,9 @@ __global__ void k_su_camera_major(int NE, const int* __restrict__ cam_ent, const
 void su_camera_major(hipStream_t s, int NE, const int* cam_ent, const int* ent_pt, const int* ent_os,
                      const int4* obs_idx, const double2* obs_xy, int* ent_pos, int* cm_pt, int4* cm_idx,
                      double2* cm_xy) {
-  constexpr int kSlotBitHere = 1 << 30;  // dab_kernels.h kSlotBit
   if (NE > 0)
     k_su_camera_major<<<su_grid(NE), kSuBlock, 0, s>>>(NE, cam_ent, ent_pt, ent_os, obs_idx, obs_xy, ent_pos, cm_pt,
-                                                       cm_idx, cm_xy, kSlotBitHere);
+                                                       cm_idx, cm_xy, kSlotBit);
 }
 
 // ---- (10) runs ----
@@ -510,10 +511,7 @@ void su_gather_at(hipStream_t s, int n, const int* idx, const int* in, int* out)
   if (n > 0) k_su_gather_at<<<su_grid(n), kSuBlock, 0, s>>>(n, idx, in, out);
 }
 
-void warm_setup() {
-  hipFuncAttributes a;
-  (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(k_su_count));
-}
+DAB_WARM_TU(k_su_count);
 
 // ---- (18) explicit-Schur pair tables (build_schur_tables, large camera sets) ----
 // ordered entry pairs (e, f) of one point with cam(e) >= cam(f), generated per point in

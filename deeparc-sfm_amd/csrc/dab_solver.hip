@@ -15,6 +15,7 @@
 // reductions are all-reduced with RCCL over xGMI; every rank then factors the same S
 // and back-substitutes its own points.
 #include "dab_handle.h"
+#include "dab_warm.h"
 
 using namespace dab;
 
@@ -307,10 +308,7 @@ void dab::launch_jacobi_scale(dab_handle* h, int nfi, int on) {
   if (NC > 0) k_scale_cams<<<grid_for(6 * NC, 256, 1 << 20), 256, 0, s>>>(NC, h->ug(), h->d_scale_c, on);
   launch_intr_scale(s, nfi, h->lz.d_zg, h->lz.d_intr_act, h->lz.d_sz, on);
 }
-void dab::warm_solver() {  // this file's code object, loaded with the others (dab_create)
-  hipFuncAttributes a;
-  (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(k_scale_points));
-}
+DAB_WARM_TU(k_scale_points);
 
 static void print_header() {
   std::printf("iter      cost      cost_change  |gradient|   |step|    tr_ratio  tr_radius  ls_iter  iter_time  total_time\n");

@@ -1,7 +1,7 @@
 // rotation.h — host-side angle-axis helpers with Ceres rotation.h semantics
 // (SURVEY App. B.1). Used by the .deeparc loader (DeepArcManager.cc:141-147 converts
 // 3x3 / quaternion input to angle-axis), the camera-centre code (Extrinsic.hh:12-17)
-// and the synthetic generator. Device code has its own inline forms in dab_kernels.hip.
+// and the synthetic generator. Device code has its own inline forms in dab_rows.h.
 #pragma once
 #include <cfloat>
 #include <cmath>
