@@ -10,6 +10,7 @@ from ._abi import (DAB_CONVERGENCE, DAB_E_INVALID, DAB_E_UNSUPPORTED, DAB_FAILUR
                    SIGNATURES, load_library, last_error)
 from ._abi import DabCovarianceInfo, DabCovarianceIntrInfo, DabCovarianceOptions
 from ._abi import DAB_INTR_CENTER, DAB_INTR_DISTORTION, DAB_INTR_FOCAL
+from ._abi import DAB_SCHUR_DIRECT, DAB_SCHUR_PAIRS, DAB_SCHUR_TILES
 from .core import CONFIGS, Problem, Solver, covariance_options, options, solve, synth, synth_config
 
 __all__ = [
@@ -21,4 +22,5 @@ __all__ = [
     "DAB_LOSS_TRIVIAL", "DAB_LOSS_HUBER", "DAB_LOSS_SOFT_L1", "DAB_LOSS_CAUCHY",
     "DAB_E_INVALID", "DAB_E_UNSUPPORTED",
     "DAB_INTR_CENTER", "DAB_INTR_FOCAL", "DAB_INTR_DISTORTION",
+    "DAB_SCHUR_PAIRS", "DAB_SCHUR_TILES", "DAB_SCHUR_DIRECT",
 ]

@@ -27,6 +27,9 @@ DAB_LOSS_CAUCHY = 3
 DAB_INTR_CENTER = 1
 DAB_INTR_FOCAL = 2
 DAB_INTR_DISTORTION = 4
+DAB_SCHUR_PAIRS = 0
+DAB_SCHUR_TILES = 1
+DAB_SCHUR_DIRECT = 2
 LOSS_KINDS = {"trivial": DAB_LOSS_TRIVIAL, "huber": DAB_LOSS_HUBER, "soft_l1": DAB_LOSS_SOFT_L1,
               "cauchy": DAB_LOSS_CAUCHY}
 
@@ -158,6 +161,8 @@ SIGNATURES = {
     "dab_get_parameters": (C.c_int, [C.c_void_p, _dp, _dp]),
     "dab_set_intrinsics_free": (C.c_int, [C.c_void_p, _u8p]),
     "dab_get_intrinsics_free": (C.c_int, [C.c_void_p, _u8p, _ip, _ip]),
+    "dab_set_points_constant": (C.c_int, [C.c_void_p, _u8p]),
+    "dab_get_points_constant": (C.c_int, [C.c_void_p, _u8p, _ip]),
     "dab_get_intrinsics": (C.c_int, [C.c_void_p, _dp]),
     "dab_update_intrinsics": (C.c_int, [C.c_void_p, _dp]),
     "dab_eval_intrinsic_jacobians": (C.c_int, [C.c_void_p, _dp]),

@@ -296,6 +296,30 @@ class Solver:
         check(self.lib.dab_get_intrinsics_free(self.h, _ptr(g, C.c_uint8), C.byref(nfi), C.byref(ns)), self.lib)
         return g, nfi.value, ns.value
 
+    def set_points_constant(self, mask):
+        """Which points the next solve and covariance hold constant (dab_set_points_constant, the
+        reference's commented-out sfm.cc:59): True / a non-zero scalar for every point, False /
+        0 / None for none, or an array of num_points (any non-zero entry = constant). Set after
+        set_problem, which resets it; it survives update_parameters and set_loss."""
+        npts = int(self.problem.points.shape[0])
+        if mask is None or (np.ndim(mask) == 0 and not mask):
+            check(self.lib.dab_set_points_constant(self.h, None), self.lib)
+            return
+        m = np.asarray(mask)
+        if m.ndim == 0:
+            m = np.full(npts, True)
+        if m.shape != (npts,):
+            raise ValueError(f"mask: a bool or {npts} values")
+        m = np.ascontiguousarray(m != 0, np.uint8)
+        check(self.lib.dab_set_points_constant(self.h, _ptr(m, C.c_uint8)), self.lib)
+
+    def get_points_constant(self):
+        """(mask [num_points] uint8 as set, points of this rank both referenced and constant)."""
+        m = np.zeros(int(self.problem.points.shape[0]), np.uint8)
+        n = C.c_int32()
+        check(self.lib.dab_get_points_constant(self.h, _ptr(m, C.c_uint8), C.byref(n)), self.lib)
+        return m, n.value
+
     def get_intrinsics(self):
         """The intrinsics on the handle, [num_intr][6] (refined ones after a solve)."""
         k = np.zeros((int(self.problem.intr.shape[0]), 6))
@@ -343,7 +367,8 @@ class Solver:
         (nfe, 6, 6) with `ext_index` (the extrinsic of each block; None on a shard whose free set
         is a union over ranks), and `ext_full` (6 nfe, 6 nfe) when full. When info["status"] is
         "RANK_DEFICIENT" the arrays are None: drop single-observation points (Problem.subset) or
-        fix the scale gauge with one more constant extrinsic. Two library calls: the size and
+        fix the scale gauge with a constant point (set_points_constant) or one more constant
+        extrinsic. Two library calls: the size and
         rank query, then the arrays.
 
         intrinsics=True: the free intrinsics of set_intrinsics_free are unknowns as well
@@ -524,13 +549,16 @@ class Solver:
 
 
 def solve(problem, max_iteration=1000, max_second=3600, freeze_camera=False, device=0,
-          verbose=False, loss=None, free_intrinsics=0, **opt_kw):
+          verbose=False, loss=None, free_intrinsics=0, freeze_points=False, **opt_kw):
     """Drop-in for the reference's solve() (src/sfm.cc:31): DENSE_SCHUR-equivalent LM,
     max_num_iterations / max_solver_time_in_seconds as given, parameters updated in place.
     loss: None (the reference's NULL loss, sfm.cc:48) or a (kind, scale) pair such as
     ("cauchy", 0.5), the `new ceres::CauchyLoss(0.5)` the reference keeps commented out.
     free_intrinsics: DAB_INTR_* bits (an int or one per intrinsic) refined with the cameras, the
-    equivalent of deleting sfm.cc:60-62; problem.intr is updated in place."""
+    equivalent of deleting sfm.cc:60-62; problem.intr is updated in place.
+    freeze_points: True (every point) or a mask of num_points: the points held constant, the
+    `SetParameterBlockConstant(parameter_block[0]); //freeze point3d` the reference keeps
+    commented out at sfm.cc:59 (pose-only refinement, ground-control points)."""
     problem.freeze_camera = bool(freeze_camera)
     o = options(max_num_iterations=max_iteration, max_solver_time_in_seconds=float(max_second),
                 minimizer_progress_to_stdout=int(verbose), **opt_kw)
@@ -541,6 +569,8 @@ def solve(problem, max_iteration=1000, max_second=3600, freeze_camera=False, dev
         s.set_problem(problem)
         if np.any(np.asarray(free_intrinsics)):
             s.set_intrinsics_free(free_intrinsics)
+        if np.any(np.asarray(freeze_points)):
+            s.set_points_constant(freeze_points)
         return s.solve(o)
     finally:
         s.close()

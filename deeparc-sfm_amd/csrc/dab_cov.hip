@@ -594,6 +594,10 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
   // free intrinsics: dab_solve's rule and refusals, before anything on the handle changes
   CamSystem cs;
   if (with_intr) CHECK_RC(cam_system_free_set(h, nullptr, &cs));
+  // constant points: PU = 0 and q = 0 take them out of S and of the fold-back (their rows of
+  // point_cov come out exactly 0), and the rank test leaves them out
+  CHECK_RC(pt_const_sync(h));
+  const int nfree_pts = h->NP - h->n_pt_const;
   hipStream_t s = h->stream;
   const DevView& v = h->view;
   const int NP = h->NP, NC = h->NC;
@@ -607,11 +611,11 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
   dab_covariance_info out{};
   out.status = DAB_COV_OK;
   out.num_free_ext = NC;
-  out.num_free_points = NP;
+  out.num_free_points = nfree_pts;
   out.first_deficient_point = -1;
   out.schur_assembly = h->schur_tiles ? DAB_SCHUR_TILES : DAB_SCHUR_PAIRS;
   out.num_residuals = 2 * h->N;
-  out.num_parameters = 3 * NP + 6 * NC + cs.nz_scal;
+  out.num_parameters = 3 * nfree_pts + 6 * NC + cs.nz_scal;
   out.point_pivot_ratio_min = out.camera_pivot_ratio = std::numeric_limits<double>::quiet_NaN();
   for (hipEvent_t& e : h->cov_ev)
     if (!e) HIP_OK(hipEventCreate(&e));
@@ -641,9 +645,9 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
   dab_options_init(&lm);
   const StepScalars sc{std::numeric_limits<double>::infinity(), lm.min_lm_diagonal, lm.max_lm_diagonal};
   HIP_OK(hipMemsetAsync(h->d_flags, 0, sizeof(int) * 4, s));
-  launch_point_factor(s, v, h->d_V, h->d_g, h->d_scale_p, sc, h->d_L, h->d_q, h->d_flags);
+  launch_point_factor_m(s, v, h->d_V, h->d_g, h->d_scale_p, sc, h->d_L, h->d_q, h->d_flags, h->d_ptc);
   double* d_ratio = h->d_dp;  // [NP] of the step buffer (scratch between LM steps)
-  launch_cov_point_rank(s, NP, h->d_V, h->d_scale_p, opt.min_pivot_ratio, d_ratio, d_rpart, rgrid);
+  launch_cov_point_rank_m(s, NP, h->d_V, h->d_scale_p, opt.min_pivot_ratio, d_ratio, d_rpart, rgrid, h->d_ptc);
   launch_final_sum(s, rgrid, 1, d_rpart, d_stat);
   CHECK_RC(h->allreduce(d_stat, 1, ncclMax));  // every rank takes the same exit
   double hstat[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -652,7 +656,7 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
   HIP_OK(hipMemcpyAsync(hmin.data(), d_rpart + rgrid, sizeof(double) * (size_t)rgrid, hipMemcpyDeviceToHost, s));
   HIP_OK(hipStreamSynchronize(s));
   CHECK_RC(p2p_check(h->p2p_main));
-  if (NP > 0) out.point_pivot_ratio_min = *std::min_element(hmin.begin(), hmin.end());
+  if (nfree_pts > 0) out.point_pivot_ratio_min = *std::min_element(hmin.begin(), hmin.end());
   auto finish = [&](hipEvent_t last) -> int {
     float ms = 0.f;
     HIP_OK(hipEventSynchronize(last));

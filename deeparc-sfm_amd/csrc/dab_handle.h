@@ -214,6 +214,8 @@ struct Knobs {
                             // instead of building them in every work-group — -1 (default) when they
                             // exist already (the LM loop: the accepted candidate's tables), 1 always
                             // (building them first where they do not), 0 never
+  int points_direct = 1;    // DAB_POINTS_DIRECT=0: the general masked step even when no rank has a free
+                            // point (the A/B of the direct camera step, S = U + D^2)
   void read() {
     auto get = [](const char* name, int& out) {
       if (const char* e = getenv(name)) out = atoi(e);
@@ -237,6 +239,7 @@ struct Knobs {
     get("DAB_SETUP_HOST", setup_host);
     get("DAB_INTR_BORDER_LDS", intr_border_lds);
     get("DAB_EVAL_SIDE", eval_side);
+    get("DAB_POINTS_DIRECT", points_direct);
   }
   // the evaluation side this build accepts from DAB_EVAL_SIDE
   bool eval_side_ok() const {
@@ -350,6 +353,14 @@ struct Handle {
   std::vector<int> intr_nf, intr_nk;
   std::vector<int2> intr_meta;            // host copy of d_intr_meta (kernels.h)
   int nfi = 0;                            // free intrinsics of the meta now on the device
+  // constant points (dab_set_points_constant). The mask is state of the handle, reset by
+  // dab_set_problem; empty = never set or NULL. pt_const_sync works out the constant set
+  // (referenced on this rank and flagged) at each call that honours it and leaves its device
+  // form in d_ptc: null while the set is empty, so that every launch is then the unmasked one.
+  std::vector<uint8_t> pt_const;          // [num_points], caller order
+  bool pt_const_dirty = false;            // lz.d_pt_const does not hold pt_const
+  const uint8_t* d_ptc = nullptr;         // [NP] device point order (lz.d_pt_const), or null
+  int n_pt_const = 0;                     // constant points of this rank (of the last sync)
   int ldz = 0;
   // Buffers allocated from `dev` by the first call that needs them (null / capacity 0: not yet).
   // They die with dev.release(): dab_set_problem resets this whole sub-object there, so a member
@@ -366,6 +377,8 @@ struct Handle {
     double *d_zg = nullptr, *d_sz = nullptr, *d_dz = nullptr, *d_znorm = nullptr, *d_zpart = nullptr;
     double *d_bpart = nullptr, *d_bsum = nullptr, *d_Sz = nullptr, *d_yz = nullptr;
     int* d_ptmask = nullptr;  // [NP] free intrinsics each point sees (k_intr_ptmask, per solve)
+    uint8_t* d_pt_const = nullptr;  // [NP] constant points, device point order (pt_const_sync)
+    double* d_zero6 = nullptr;      // [6 NC] zeros: the rhs part of a step without free points
     size_t bpart_cap = 0, Sz_cap = 0;
     // dab_covariance: Z = L^-1 [n][lds], the point blocks [NP][6], the extrinsic blocks [NC][21],
     // the rank test's scalars and partials
@@ -632,6 +645,10 @@ int guard_fail(dab_handle* h, const char* where, Dev* extra = nullptr);
 bool intr_mask_any(const dab_handle* h);
 int intr_free_set(dab_handle* h, bool with_mask, int* nfi_out, int* nscal_out = nullptr);
 int intr_eval(dab_handle* h);
+
+// ---- dab_problem.hip: constant points ----
+// the constant set of the mask on the handle -> h->d_ptc / h->n_pt_const (uploaded when changed)
+int pt_const_sync(dab_handle* h);
 
 // ---- dab_schur_tables.hip: tables and buffers of the linear solvers, built on first use ----
 int build_schur_tables(dab_handle* h);

@@ -305,6 +305,29 @@ void launch_candidate(hipStream_t s, const DevView& v, const double* points, con
 void launch_grad_points(hipStream_t s, int NP, const double* x, const double* g /*[3][NP]*/,
                         double* partial, int grid);
 
+// ---- constant points (dab_set_points_constant; dab_k_ptconst.hip) ---------------------------
+// mask[NP], device point order, non-zero = constant. The masked forms of the small point-side
+// kernels, launched only where the constant set is not empty (a null mask is the unmasked
+// launch): free points go through the arithmetic of the kernels above, constant ones get
+// PU = 0 and q = 0 (so they drop out of Y, S, every rhs, both back substitutions, the intrinsic
+// border and the covariance's fold-back), scale 1, x_c = x bitwise, and no part in any norm, in
+// the fail flag or in the covariance's rank test.
+void launch_point_factor_m(hipStream_t s, const DevView& v, const double* V, const double* g, const double* scale_p,
+                           StepScalars sc, double* PU, double* q, int* fail, const uint8_t* mask);
+void launch_scale_points_m(hipStream_t s, int NP, const double* V, double* scale_p, int on, const uint8_t* mask);
+void launch_axpy_points_m(hipStream_t s, int NP, const double* x, const double* d, double* xc, double* partial,
+                          int grid, const uint8_t* mask);
+void launch_grad_points_m(hipStream_t s, int NP, const double* x, const double* g, double* partial, int grid,
+                          const uint8_t* mask);
+void launch_cov_point_rank_m(hipStream_t s, int NP, const double* V, const double* scale_p, double thr, double* ratio,
+                             double* partial, int grid, const uint8_t* mask);
+// No free point on any rank and no cross block: the camera system is block diagonal. Per free
+// camera H = s U s + D^2 (D^2 as k_s_diag forms it), 6x6 Cholesky in registers, yc = H^-1 (s g_c);
+// a non-positive or non-finite pivot sets bit 1 of *fail (the dense factor's "not positive
+// definite")
+void launch_cam_block_solve(hipStream_t s, int NC, const double* ug, const double* scale_c, StepScalars sc,
+                            double* yc, int* fail);
+
 // ---- free intrinsics in the exact Schur step (dab_set_intrinsics_free; dab_k_intr.hip) -----
 // meta[NI]: x = free intrinsic index or -1; y = active columns (bits 0..5: cx cy f0 f1 k0 k1
 // selected by the mask and present in the model) | columns present in the model << 8 |

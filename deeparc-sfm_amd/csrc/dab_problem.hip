@@ -1269,6 +1269,58 @@ extern "C" int dab_get_intrinsic_blocks(dab_handle* h, int32_t* num_free_intr, d
   return 0;
 }
 
+// ------------------------------------------------------------------------------------
+// constant points: host state
+// ------------------------------------------------------------------------------------
+// The constant set of the mask on the handle (referenced here and flagged), in device point
+// order, for the calls that honour it. Empty: d_ptc stays null and nothing touches the device.
+int dab::pt_const_sync(dab_handle* h) {
+  h->d_ptc = nullptr;
+  h->n_pt_const = 0;
+  if (h->pt_const.empty() || h->NP <= 0) return 0;
+  std::vector<uint8_t> m((size_t)h->NP);
+  int n = 0;
+  for (int i = 0; i < h->NP; ++i) n += (m[(size_t)i] = h->pt_const[(size_t)h->pt_of[(size_t)i]] != 0);
+  if (n == 0) return 0;
+  if (!h->lz.d_pt_const) {
+    CHECK_RC(h->dev.alloc(&h->lz.d_pt_const, (size_t)h->NP));
+    h->pt_const_dirty = true;
+  }
+  if (h->pt_const_dirty) {
+    HIP_OK(hipMemcpyAsync(h->lz.d_pt_const, m.data(), m.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));  // m goes out of scope
+    h->pt_const_dirty = false;
+  }
+  h->d_ptc = h->lz.d_pt_const;
+  h->n_pt_const = n;
+  return 0;
+}
+extern "C" int dab_set_points_constant(dab_handle* h, const uint8_t* mask) {
+  clear_error();
+  if (!h) return set_error(DAB_E_INVALID, "null handle");
+  if (!h->have_problem) return set_error(DAB_E_STATE, "no problem set");
+  const size_t n = (size_t)h->prob.num_points;
+  if (mask) h->pt_const.assign(mask, mask + n);
+  else h->pt_const.clear();
+  h->pt_const_dirty = true;
+  return 0;
+}
+extern "C" int dab_get_points_constant(dab_handle* h, uint8_t* mask, int32_t* num_constant) {
+  clear_error();
+  if (!h) return set_error(DAB_E_INVALID, "null handle");
+  if (!h->have_problem) return set_error(DAB_E_STATE, "no problem set");
+  const size_t n = (size_t)h->prob.num_points;
+  if (mask)
+    for (size_t i = 0; i < n; ++i) mask[i] = h->pt_const.empty() ? 0 : h->pt_const[i];
+  if (num_constant) {
+    int c = 0;
+    if (!h->pt_const.empty())
+      for (int i = 0; i < h->NP; ++i) c += h->pt_const[(size_t)h->pt_of[(size_t)i]] != 0;
+    *num_constant = c;
+  }
+  return 0;
+}
+
 extern "C" int dab_set_problem(dab_handle* h, const dab_problem* p) {
   const int rc = set_problem_impl(h, p);
   CHECK_RC(guard_fail(h, "dab_set_problem"));
@@ -1288,6 +1340,10 @@ static int set_problem_impl(dab_handle* h, const dab_problem* p) {
   h->lz = dab_handle::Lazy{};
   h->have_problem = false;
   h->prob = *p;
+  h->pt_const.clear();  // all free again (num_points may have changed)
+  h->pt_const_dirty = true;
+  h->d_ptc = nullptr;
+  h->n_pt_const = 0;
   PhaseTimer phase{"set_problem %-22s %8.1f ms\n"};  // the host preprocessing's phases
   const int N = p->num_obs;
   h->N = N;

@@ -241,7 +241,7 @@ int dab::eval_jacobian_and_blocks(dab_handle* h, bool with_norms, bool tables_cu
   if (!tables_current) launch_cam_tables(s, h->E, h->d_ext, h->d_camtab);
   CHECK_RC(eval_pass(h, true));
   if (with_norms) {
-    launch_grad_points(s, h->NP, h->d_points, h->d_g, h->d_gpart, h->red_grid);
+    launch_grad_points_m(s, h->NP, h->d_points, h->d_g, h->d_gpart, h->red_grid, h->d_ptc);
     launch_final_sum(s, h->red_grid, 3, h->d_gpart, h->d_scal + S_GMAX_P, 1u);
     launch_cam_norms(s, h->E, h->d_ext_col, h->d_ext, nullptr, h->NC > 0 ? h->ug() : nullptr,
                      h->d_scal + S_CAM0);
@@ -304,7 +304,8 @@ __global__ void k_scale_cams(int NC, const double* __restrict__ ug, double* __re
 void dab::launch_jacobi_scale(dab_handle* h, int nfi, int on) {
   hipStream_t s = h->stream;
   const int NP = h->NP, NC = h->NC;
-  k_scale_points<<<grid_for(3 * NP, 256, 1 << 20), 256, 0, s>>>(NP, h->d_V, h->d_scale_p, on);
+  if (h->d_ptc) launch_scale_points_m(s, NP, h->d_V, h->d_scale_p, on, h->d_ptc);
+  else k_scale_points<<<grid_for(3 * NP, 256, 1 << 20), 256, 0, s>>>(NP, h->d_V, h->d_scale_p, on);
   if (NC > 0) k_scale_cams<<<grid_for(6 * NC, 256, 1 << 20), 256, 0, s>>>(NC, h->ug(), h->d_scale_c, on);
   launch_intr_scale(s, nfi, h->lz.d_zg, h->lz.d_intr_act, h->lz.d_sz, on);
 }
@@ -333,6 +334,24 @@ static double elapsed_collective(dab_handle* h, double local) {
     return -1.0;
   if (hipStreamSynchronize(s) != hipSuccess) return -1.0;
   return h->h_scal[S_TIME];
+}
+
+// Constant points, decided once per solve for all ranks with one max-reduce: 2 when some rank has
+// a free referenced point, 1 when none has and some rank has a constant one (no free point in the
+// problem), 0 when there are no referenced points at all. Expects pt_const_sync's counts.
+static int points_state(dab_handle* h, int* state) {
+  double local = h->NP - h->n_pt_const > 0 ? 2.0 : (h->n_pt_const > 0 ? 1.0 : 0.0);
+  if (h->coll()) {
+    hipStream_t s = h->stream;
+    h->h_scal[S_TIME] = local;
+    HIP_OK(hipMemcpyAsync(h->d_scal + S_TIME, &h->h_scal[S_TIME], sizeof(double), hipMemcpyHostToDevice, s));
+    CHECK_RC(h->allreduce(h->d_scal + S_TIME, 1, ncclMax));
+    HIP_OK(hipMemcpyAsync(&h->h_scal[S_TIME], h->d_scal + S_TIME, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    local = h->h_scal[S_TIME];
+  }
+  *state = (int)local;
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------
@@ -510,21 +529,43 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
       opt.linear_solver_type != DAB_LINEAR_SOLVER_IMPLICIT_SCHUR_PCG &&
       opt.linear_solver_type != DAB_LINEAR_SOLVER_AUTO)
     return set_error(DAB_E_INVALID, "unknown linear_solver_type");
+  HIP_OK(hipSetDevice(h->device));
+  // constant points: this rank's set, and whether any rank has a free point left
+  CHECK_RC(pt_const_sync(h));
+  int pstate = 2;
+  CHECK_RC(points_state(h, &pstate));
+  const bool no_free_points = pstate == 1;
   if (opt.linear_solver_type == DAB_LINEAR_SOLVER_AUTO)  // the same choice on every rank (NC is the union's)
-    opt.linear_solver_type = h->world <= 1 || h->NC == 0 || mf_schur_fits(h->NC, h->E, h->NI)
+    opt.linear_solver_type = h->world <= 1 || h->NC == 0 || mf_schur_fits(h->NC, h->E, h->NI) ||
+                                     (no_free_points && h->knobs.points_direct != 0)  // S = U + D^2: nothing to reduce
                                  ? DAB_LINEAR_SOLVER_EXPLICIT_SCHUR
                                  : DAB_LINEAR_SOLVER_IMPLICIT_SCHUR_PCG;
   const bool use_pcg = opt.linear_solver_type == DAB_LINEAR_SOLVER_IMPLICIT_SCHUR_PCG;
-  HIP_OK(hipSetDevice(h->device));
   const bool timing = PhaseTimer::on();
   // free intrinsics: the refusals come first, so a refused solve leaves the handle as it was
   CamSystem cs;
   CHECK_RC(cam_system_free_set(
       h, use_pcg ? "free intrinsics need the exact step (DAB_LINEAR_SOLVER_EXPLICIT_SCHUR)" : nullptr, &cs));
+  // no free point on any rank: no Schur complement, the camera system is U + D^2 (block diagonal
+  // without cross blocks). Not with free intrinsics, nor for an explicitly requested PCG
+  const bool direct = no_free_points && !use_pcg && cs.nfi == 0 && h->NC > 0 && h->knobs.points_direct != 0;
+  const bool direct_dense = direct && h->ncross > 0;
+  const bool no_free_params = no_free_points && h->NC == 0;
   const double tp0 = now_s();
-  CHECK_RC(use_pcg ? build_pcg_buffers(h) : build_schur_tables(h));
+  if (direct_dense) {
+    // the dense buffer as build_schur_tables sizes it (kept when the tables are built later)
+    const int nd = 6 * h->NC;
+    h->lds = ((nd + 1 + 7) / 8) * 8;
+    if (h->lds % 512 == 0) h->lds += 8;
+    CHECK_RC(h->sticky(h->st_S, &h->d_S, (size_t)(nd + 1) * h->lds));
+    if (!h->lz.d_zero6) {
+      CHECK_RC(h->dev.alloc(&h->lz.d_zero6, (size_t)nd));
+      HIP_OK(hipMemsetAsync(h->lz.d_zero6, 0, sizeof(double) * (size_t)nd, h->stream));
+    }
+  }
+  if (!direct && !no_free_params) CHECK_RC(use_pcg ? build_pcg_buffers(h) : build_schur_tables(h));
   const double tp1 = now_s();
-  CHECK_RC(cam_system_buffers(h, !use_pcg, &cs));
+  CHECK_RC(cam_system_buffers(h, direct ? direct_dense : !use_pcg && !no_free_params, &cs));
   const int nfi = cs.nfi, n2 = cs.n2;
   double* const yc_ = cs.yc;
   if (timing)
@@ -550,8 +591,8 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
   sum->num_successful_steps = sum->num_unsuccessful_steps = 0;
   sum->num_iterations = 0;
   sum->num_residuals = 2 * h->N;
-  sum->num_parameters = 3 * NP + 6 * NC + cs.nz_scal;
-  sum->num_free_points = NP;
+  sum->num_parameters = 3 * (NP - h->n_pt_const) + 6 * NC + cs.nz_scal;
+  sum->num_free_points = NP - h->n_pt_const;
   sum->num_free_ext = NC;
   sum->jacobian_evaluation_time_in_seconds = 0;
   sum->residual_evaluation_time_in_seconds = 0;
@@ -559,13 +600,15 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
   sum->termination_type = DAB_FAILURE;
   sum->linear_solver_type_used = opt.linear_solver_type;
   sum->schur_assembly = use_pcg ? (h->mf ? (h->mf32 ? DAB_PCG_MATRIX_FREE_FP32 : DAB_PCG_MATRIX_FREE) : DAB_PCG_STORED_Y)
-                                : (h->schur_tiles ? DAB_SCHUR_TILES : DAB_SCHUR_PAIRS);
+                                : (direct ? DAB_SCHUR_DIRECT : h->schur_tiles ? DAB_SCHUR_TILES : DAB_SCHUR_PAIRS);
   const bool verbose = opt.minimizer_progress_to_stdout && h->rank == 0;
 
   // ---- iteration 0 ----
   // a solve starts with a clean sticky error word (a timed-out wait of an earlier call was
   // reported by that call)
   HIP_OK(hipMemsetAsync(h->d_scal + S_XERR, 0, sizeof(double), s));
+  // without free points no back substitution runs: delta_p is zero for the whole solve
+  if (direct && NP > 0) HIP_OK(hipMemsetAsync(h->d_dp, 0, sizeof(double) * 3 * (size_t)NP, s));
   double t0 = now_s();
   CHECK_RC(eval_jacobian_and_blocks(h, true));
   // intrinsic sums and norms at x (k_intr_eval after every evaluation pass); hz = their host copy:
@@ -603,6 +646,15 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
   if (!eval_ok) {
     std::snprintf(sum->message, sizeof(sum->message), "Residual and Jacobian evaluation failed.");
     sum->final_cost = x_cost;
+    sum->total_time_in_seconds = now_s() - t_start;
+    return 0;
+  }
+  if (no_free_params) {
+    // Ceres' reduced program is empty: nothing to minimise, the parameters stay as they are
+    sum->termination_type = DAB_CONVERGENCE;
+    sum->final_cost = x_cost;
+    std::snprintf(sum->message, sizeof(sum->message),
+                  "Function tolerance reached. No non-constant parameter blocks found.");
     sum->total_time_in_seconds = now_s() - t_start;
     return 0;
   }
@@ -667,9 +719,16 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
     const double tls = now_s();
     StepScalars sc{radius, opt.min_lm_diagonal, opt.max_lm_diagonal};
     HIP_OK(hipMemsetAsync(h->d_flags, 0, sizeof(int) * 4, s));
-    launch_point_factor(s, v, h->d_V, h->d_g, h->d_scale_p, sc, h->d_L, h->d_q, h->d_flags);
+    if (!direct) launch_point_factor_m(s, v, h->d_V, h->d_g, h->d_scale_p, sc, h->d_L, h->d_q, h->d_flags, h->d_ptc);
     bool pcg_fail = false;
-    if (NC > 0 && use_pcg) {
+    if (direct && !direct_dense) {
+      launch_cam_block_solve(s, NC, h->ug(), h->d_scale_c, sc, yc_, h->d_flags + 1);
+    } else if (direct) {
+      HIP_OK(hipMemsetAsync(cs.S, 0, sizeof(double) * (size_t)(n + 1) * cs.ld, s));
+      launch_s_add_u(s, NC, h->ug(), h->ncross, h->d_cross_cam, h->Ux(), h->d_scale_c, sc, h->lz.d_zero6, cs.S, cs.ld);
+      if (chol_factor_solve(h->chol, s, n, cs.S, cs.ld, yc_, h->d_flags + 1) != 0)
+        return set_error(DAB_E_DEVICE, "dense Cholesky launch failed");
+    } else if (NC > 0 && use_pcg) {
       if (!h->mf) launch_entry_y(s, v, h->d_points, h->d_camtab, h->d_scale_c, h->d_L, yb, true);
       int cg_iters = 0, cg_status = 0;
       CHECK_RC(pcg_solve(h, opt, sc, yb, &cg_iters, &cg_status));
@@ -681,15 +740,16 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
       if (chol_factor_solve(h->chol, s, n2, cs.S, cs.ld, yc_, h->d_flags + 1) != 0)
         return set_error(DAB_E_DEVICE, "dense Cholesky launch failed");
     }
-    if ((use_pcg && h->mf) || (!use_pcg && h->schur_tiles))
+    // (the direct step has no back substitution: delta_p stays the zeros written before iteration 0)
+    if (!direct && ((use_pcg && h->mf) || (!use_pcg && h->schur_tiles)))
       launch_mf_backsub(s, v, h->d_points, h->d_camtab, h->d_scale_c, h->d_L, h->d_q, yc_, h->d_dp, h->mf_grid_n);
-    else
+    else if (!direct)
       launch_backsub(s, v, h->d_L, h->d_q, yb, NC > 0 ? yc_ : nullptr, h->d_dp);
     // the y_z term of the point step, whichever back substitution ran
     if (nfi > 0)
       launch_intr_backsub(s, v, h->d_points, h->d_camtab, h->d_L, h->lz.d_sz, yc_ + n, h->lz.d_intr_meta, h->d_dp);
     // candidate x + delta and the model / candidate cost in one observation pass
-    launch_axpy_points(s, NP, h->d_points, h->d_dp, h->d_points_c, h->d_gpart, h->red_grid);
+    launch_axpy_points_m(s, NP, h->d_points, h->d_dp, h->d_points_c, h->d_gpart, h->red_grid, h->d_ptc);
     launch_final_sum(s, h->red_grid, 2, h->d_gpart, h->d_scal + S_STEP_P);
     launch_cam_candidate(s, h->E, h->d_ext_col, h->d_ext, NC > 0 ? yc_ : nullptr, h->d_scale_c, h->d_ext_c,
                          h->d_dc);

@@ -64,6 +64,13 @@ class DeepArcManager {
   // pointers; quirk Q1's truncation is the reader's), so write() and the accessors see them.
   void setIntrinsicsFree(int groups) { intr_free_ = groups; }
   int intrinsicsFree() const { return intr_free_; }
+  // sfm.cc:59, `//problem.SetParameterBlockConstant(parameter_block[0]); //freeze point3d`,
+  // uncommented: every later solve() of this manager holds all points constant
+  // (dab_set_points_constant with an all-ones mask; all or nothing, as that line is) and refines
+  // the cameras alone. Kept across the pipeline's re-set-ups beside the loss and the intrinsic
+  // groups and applied after every dab_set_problem.
+  void setPointsConstant(bool all) { points_const_ = all; }
+  bool pointsConstant() const { return points_const_; }
 
   // Covariance of the current scene at its current parameters (dab_covariance in dab.h: Sigma =
   // (J^T J)^-1 under this manager's loss, no sigma^2 factor; ceres::Covariance). The reference's
@@ -103,6 +110,7 @@ class DeepArcManager {
   int loss_type_ = 0;  // DAB_LOSS_TRIVIAL
   double loss_scale_ = 1.0;
   int intr_free_ = 0;  // all constant (sfm.cc:60-62)
+  bool points_const_ = false;  // all free (sfm.cc:59 commented out)
   int arc_size_ = 0, ring_size_ = 0;
   bool share_extrinsic_ = false;
   std::map<int, std::map<int, Camera*> > hemisphere_;

@@ -151,6 +151,13 @@ int dam_set_intrinsics_free(dam_manager* m, int32_t groups) {
   });
 }
 
+int dam_set_points_constant(dam_manager* m, int32_t all) {
+  return guarded([&] {
+    if (!m) throw "null manager";
+    m->m.setPointsConstant(all != 0);
+  });
+}
+
 int dam_covariance(dam_manager* m, const int32_t* extra_const, int32_t n_extra, int32_t freeze_camera,
                    double* point_cov, double* ext_cov, double* ext_full, int32_t* ext_label,
                    dab_covariance_info* info) {

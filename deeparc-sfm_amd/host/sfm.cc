@@ -34,6 +34,14 @@ int solveWith(DeepArcManager& m, const dab_options& options, bool freeze_camera,
     rc = dab_set_intrinsics_free(dh.h, nullptr);
   }
   if (rc) return rc;
+  // sfm.cc:59 for every point, or for none: after every (re-)set-up, like the groups above
+  if (m.pointsConstant()) {
+    const std::vector<uint8_t> all((size_t)scene.problem.num_points, (uint8_t)1);
+    rc = dab_set_points_constant(dh.h, all.data());
+  } else {
+    rc = dab_set_points_constant(dh.h, nullptr);
+  }
+  if (rc) return rc;
   const double t0 = dab_now_seconds();
   rc = dab_solve(dh.h, &options, s);
   // (not with free intrinsics: they need the exact step, and PCG's refusal would hide the reason)

@@ -46,6 +46,7 @@ SIGNATURES = {
                             C.POINTER(_abi.DabSummary)]),
     "dam_set_loss": (C.c_int, [C.c_void_p, C.c_int32, C.c_double]),
     "dam_set_intrinsics_free": (C.c_int, [C.c_void_p, C.c_int32]),
+    "dam_set_points_constant": (C.c_int, [C.c_void_p, C.c_int32]),
     "dam_covariance": (C.c_int, [C.c_void_p, _ip, C.c_int32, C.c_int32, _dp, _dp, _dp, _ip,
                                  C.POINTER(_abi.DabCovarianceInfo)]),
     "dam_covariance_intrinsics": (C.c_int, [C.c_void_p, _ip, C.c_int32, _dp, _dp, _dp, _dp, _ip, _ip,
@@ -155,6 +156,11 @@ class DeepArcManager:
         (dam_set_intrinsics_free): the equivalent of deleting sfm.cc:60-62. cameras() and write()
         see the refined values."""
         _check(self.lib.dam_set_intrinsics_free(self.h, int(groups)))
+
+    def set_points_constant(self, all_points=True):
+        """Every later solve() of this manager holds all points constant (dam_set_points_constant):
+        the reference's commented-out sfm.cc:59; False frees them again."""
+        _check(self.lib.dam_set_points_constant(self.h, int(bool(all_points))))
 
     def covariance(self, extra_const=(), freeze_camera=False, full=False):
         """DeepArcManager::covariance (dam_covariance): the covariance of the current scene at its

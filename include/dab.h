@@ -63,10 +63,10 @@ extern "C" {
  * intr_nk[i] in {0,1,2} (Intrinsic.hh:32; unused slots ignored).
  * Intrinsics are constant by default, as in the reference (sfm.cc:54-63);
  * dab_set_intrinsics_free frees them by group for the exact step.
- * Constancy: points are free; an extrinsic is free unless ext_const[e] != 0 or
- * freeze_camera != 0 (sfm.cc:50-57). Parameter blocks referenced by no observation
- * are not part of the problem (Ceres only knows blocks added via AddResidualBlock)
- * and are left untouched.
+ * Constancy: points are free unless dab_set_points_constant holds them (sfm.cc:59); an
+ * extrinsic is free unless ext_const[e] != 0 or freeze_camera != 0 (sfm.cc:50-57). Parameter
+ * blocks referenced by no observation are not part of the problem (Ceres only knows blocks
+ * added via AddResidualBlock) and are left untouched.
  */
 typedef struct dab_problem {
   int32_t num_obs;
@@ -171,6 +171,7 @@ typedef struct dab_summary {
 /* schur_assembly values for DAB_LINEAR_SOLVER_EXPLICIT_SCHUR */
 #define DAB_SCHUR_PAIRS 0   /* per camera-pair block sums over entry-pair tables (large NC) */
 #define DAB_SCHUR_TILES 1   /* register-owned block tiles over per-step Y records (NC <= 160) */
+#define DAB_SCHUR_DIRECT 2  /* no free point on any rank: S = U + D^2, no Schur complement */
 /* schur_assembly values for DAB_LINEAR_SOLVER_IMPLICIT_SCHUR_PCG */
 #define DAB_PCG_STORED_Y 0          /* products over stored Y records (fp32 records with pcg_fp32) */
 #define DAB_PCG_MATRIX_FREE 1       /* rows re-evaluated per product, all fp64 (NC <= 160) */
@@ -321,6 +322,60 @@ int dab_update_intrinsics(dab_handle* h, const double* intr);
 int dab_eval_intrinsic_jacobians(dab_handle* h, double* J /* [num_obs][2][6], caller order */);
 int dab_get_intrinsic_blocks(dab_handle* h, int32_t* num_free_intr, double* zg /* [nfi][27] = U_zz upper 21 | g_z 6 */);
 
+/* ---- constant points --------------------------------------------------------------------
+ * sfm.cc:59 keeps `//problem.SetParameterBlockConstant(parameter_block[0]); //freeze point3d`
+ * commented out beside the three intrinsic freezes. Here it is a mask on the handle, one byte
+ * per point in the caller's order (any non-zero byte = constant; NULL = all free, the default):
+ * pose-only refinement against a trusted model (all points), ground-control points (a few, which
+ * also fix the scale gauge dab_covariance needs), resectioning.
+ *
+ * The mask is state of the handle, set after dab_set_problem; dab_set_problem resets it to
+ * all-free (num_points may change); it survives dab_update_parameters and dab_set_loss and
+ * takes effect at the next dab_solve, dab_covariance or dab_covariance_intrinsics. A flagged
+ * point that no observation references is ignored, as unreferenced blocks are everywhere else.
+ * In a multi-rank handle each rank passes the mask of its own shard (the calls that honour it are
+ * collective already). dab_get_points_constant returns the mask as set (zeros when never set)
+ * and in *num_constant the points of this rank that are both referenced and constant.
+ *
+ * A constant point is out of the problem, as in Ceres' reduced program: it is not counted in
+ * num_parameters or num_free_points (dab_summary, dab_covariance_info), takes no part in
+ * gradient_max_norm, x_norm or step_norm, has no Jacobi scale or LM diagonal of its own; its
+ * observations still contribute residuals, cost and camera (and intrinsic) rows in full.
+ * dab_solve never writes it: its three doubles in the caller's `points` and in
+ * dab_get_parameters are bitwise the input, also after rejected steps. With an empty constant
+ * set (never set, NULL, all zero, or only unreferenced points flagged) every call gives bitwise
+ * what it gives on a handle that never set a mask.
+ *
+ * The step. With some points free: the exact or PCG step as before, the constant points' PU and
+ * q set to zero ("Constant points"); every linear solver, assembly, loss and
+ * free-intrinsics combination that works without a mask works with one. With no free referenced
+ * point on any rank (decided collectively, once per solve), an empty free-intrinsics set and
+ * EXPLICIT_SCHUR (requested, or AUTO, which then resolves to EXPLICIT_SCHUR on any world size:
+ * U is all-reduced by the evaluation pass already), there is no Schur complement: S = U + D^2,
+ * summary.schur_assembly = DAB_SCHUR_DIRECT. Without arc-ring cross blocks S is block diagonal
+ * and every camera's 6x6 block is solved on its own (no dense S is allocated); with cross blocks
+ * (the rig) S is filled from U and factored densely. No point factor, Y or pair / tile tables
+ * either way. DAB_POINTS_DIRECT=0 in the environment (read at dab_create) forces the general
+ * masked step for this case; so do a non-empty free-intrinsics set and an explicitly requested
+ * IMPLICIT_SCHUR_PCG.
+ *
+ * No free parameter at all (every referenced point constant, and freeze_camera or no free
+ * extrinsic): dab_solve returns DAB_OK with DAB_CONVERGENCE, num_iterations = 0, no iteration
+ * record, initial_cost == final_cost and Ceres' message "Function tolerance reached. No
+ * non-constant parameter blocks found."; the parameters are untouched.
+ *
+ * Covariance: Sigma is over the free points, the free extrinsics and (second call) the active
+ * intrinsic scalars; point_cov rows of constant points are exactly 0 (known exactly, as
+ * intr_cov's inactive slots), unreferenced points stay NaN, and constant points are left out of
+ * the point rank test, deficient_points and first_deficient_point. With every point constant
+ * Sigma_cc = U^-1.
+ *
+ * dab_eval_residuals, dab_eval_jacobians, dab_filter, dab_bench_eval_pass and
+ * dab_bench_get_blocks ignore the mask (raw quantities). Errors: DAB_E_INVALID for a null handle
+ * (checked before any device use); DAB_E_STATE before dab_set_problem. */
+int dab_set_points_constant(dab_handle* h, const uint8_t* mask /* [num_points], caller order; NULL = all free */);
+int dab_get_points_constant(dab_handle* h, uint8_t* mask /* nullable */, int32_t* num_constant /* nullable */);
+
 /* ---- evaluation (parity / filterPoint3d) ---------------------------------------------
  * residuals: [num_obs][2] in the caller's observation order.
  * jacobians: [num_obs][2][15] row-major, columns = [X(3) | w0(3) t0(3) | w1(3) t1(3)]
@@ -384,7 +439,8 @@ int dab_filter(dab_handle* h, double error_boundary, const double center[3], dou
  * first_deficient_point / deficient_points, the camera side camera_pivot_ratio (0 when the
  * factor met a non-positive pivot). Deficient points are not skipped: their observations would
  * still sit in U and S would be overconfident. Remedies: drop such points from the problem
- * (Problem.subset in the Python layer), and fix the scale gauge with one more constant extrinsic
+ * (Problem.subset in the Python layer), and fix the scale gauge with one constant point
+ * (dab_set_points_constant: a ground-control point) or with one more constant extrinsic
  * (ext_const) beside the reference's arc 0 / camera 0.
  *
  * Multi-rank handles: every rank calls it. S is all-reduced as in the exact step, every rank

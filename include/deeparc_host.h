@@ -60,6 +60,11 @@ int dam_set_loss(dam_manager* m, int32_t loss_type, double scale);
  * intrinsics untruncated, so dam_get_cameras and dam_write see them. Bits above 7 return an
  * error and leave the setting as it was. */
 int dam_set_intrinsics_free(dam_manager* m, int32_t groups);
+/* all != 0: every later solve of this manager holds every point constant and refines the cameras
+ * alone (dab_set_points_constant with every point flagged: the reference's commented-out
+ * sfm.cc:59, all or nothing as that line is). 0, the default, frees them again. Re-applied after
+ * every re-set of the resident problem, like the loss and the intrinsic groups. */
+int dam_set_points_constant(dam_manager* m, int32_t all);
 /* DeepArcManager::covariance: dab_covariance (dab.h) of the manager's current scene at its
  * current parameters, under the manager's loss. extra_const[n_extra]: extrinsic indices held
  * constant beside the gauge rule's; the reference's rule leaves the rig's global scale free

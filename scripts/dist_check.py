@@ -11,6 +11,10 @@ robust loss (dab_set_loss) on every rank's handle and on the single handle it is
 --free-intrinsics G sets the DAB_INTR_* groups G free on every intrinsic (dab_set_intrinsics_free),
 on every rank's handle and on the single handle; the refined intrinsics are compared too (the exact
 step only: pair it with --solvers explicit).
+--const-points third|all holds every third point (by global id), or every point, constant
+(dab_set_points_constant) on every rank's shard and on the single handle; the constant points must
+come back bitwise untouched, and with `all` every rank must report the direct camera step
+(DAB_SCHUR_DIRECT) for the explicit and the AUTO solver (pair it with --solvers explicit,auto).
 --expect-auto-refused checks instead that LINEAR_SOLVER_AUTO, where it picks PCG (several ranks, a
 camera system that is not a small one), refuses a non-empty free set on every rank.
 --covariance checks dab_covariance instead: every rank calls it on its shard after the solve, and
@@ -61,6 +65,9 @@ def main():
     ap.add_argument("--free-intrinsics", type=int, default=0,
                     help="DAB_INTR_* group bits refined on every handle (every rank sets the same mask); the "
                     "result is compared with the single handle at --tol")
+    ap.add_argument("--const-points", default="", choices=("", "third", "all"),
+                    help="constant points on every handle: every third point by global id, or all of them (then "
+                    "every rank must take the direct camera step, S = U + D^2, also under AUTO)")
     ap.add_argument("--expect-auto-refused", action="store_true",
                     help="with --free-intrinsics: a rig whose tables do not fit the small-camera paths (135 "
                     "extrinsics), so AUTO picks PCG on several ranks; every rank's dab_solve must return "
@@ -248,6 +255,11 @@ def main():
         else:
             glob = pkg.synth(**pkg.CONFIGS[kind])
         owner = glob.point_owner(world)
+        cmask = None
+        if a.const_points:
+            cmask = np.ones(glob.points.shape[0], bool)
+            if a.const_points == "third":
+                cmask = np.arange(glob.points.shape[0]) % 3 == 0
         live = []
         if a.live_together:  # every handle of this problem created (and its arena slot taken) up front
             for _ in range(3):
@@ -266,12 +278,14 @@ def main():
                 s1.set_problem(g1)
                 if a.free_intrinsics:
                     s1.set_intrinsics_free(a.free_intrinsics)
+                if cmask is not None:
+                    s1.set_points_constant(cmask)
                 ropts = opts
                 if lst == pkg.DAB_LINEAR_SOLVER_AUTO:
                     # what AUTO must pick on several ranks: the exact step for small camera
                     # systems (the rig), PCG for large ones (BAL / config 4)
-                    want = (pkg.DAB_LINEAR_SOLVER_EXPLICIT_SCHUR if glob.ext.shape[0] <= 160
-                            else pkg.DAB_LINEAR_SOLVER_IMPLICIT_SCHUR_PCG)
+                    want = (pkg.DAB_LINEAR_SOLVER_EXPLICIT_SCHUR
+                            if glob.ext.shape[0] <= 160 or a.const_points == "all" else pkg.DAB_LINEAR_SOLVER_IMPLICIT_SCHUR_PCG)
                     ropts = pkg.options(max_num_iterations=a.iters, linear_solver_type=want)
                 ref = (s1.solve(ropts), g1.points.copy(), g1.ext.copy(), g1.intr.copy())
                 s1.close()
@@ -284,6 +298,8 @@ def main():
             s.set_problem(mine)
             if a.free_intrinsics:
                 s.set_intrinsics_free(a.free_intrinsics)  # the same mask on every rank (include/dab.h)
+            if cmask is not None:
+                s.set_points_constant(cmask)  # the shard's points are the ones this rank references
             sched = s.eval_fused()
             p2p = s.comm_p2p()
             summ = s.solve(opts)
@@ -299,6 +315,11 @@ def main():
             dist.all_reduce(kk, op=dist.ReduceOp.MAX)
             kk_min = torch.from_numpy(mine.intr.copy())
             dist.all_reduce(kk_min, op=dist.ReduceOp.MIN)
+            asm = torch.tensor([summ["schur_assembly"], -summ["schur_assembly"]], dtype=torch.int32)
+            dist.all_reduce(asm, op=dist.ReduceOp.MAX)  # (max, -min) over the ranks
+            held = True if cmask is None else bool(np.array_equal(mine.points[cmask], glob.points[cmask]))
+            held = torch.tensor([1 if held else 0], dtype=torch.int32)
+            dist.all_reduce(held, op=dist.ReduceOp.MIN)
             if rank == 0:
                 rs, rp, re, rk = ref
                 ca = [it["cost"] for it in summ["iterations"]]
@@ -319,6 +340,7 @@ def main():
                     intr_moved=float(np.abs(rk - glob.intr).max()) if rk.size else 0.0,
                     num_parameters=(summ["num_parameters"], rs["num_parameters"]),
                     eval_schedule=sched, p2p=p2p,
+                    assembly=(int(asm[0]), -int(asm[1]), rs["schur_assembly"]), const_held=bool(held.item()),
                     solver_used=(summ["linear_solver_type_used"], rs["linear_solver_type_used"]))
         for h in live:
             h.close()
@@ -336,6 +358,9 @@ def main():
                or (not k.startswith("rig") and v["eval_schedule"] != 2)  # BAL shards: the split fused pass
                or (a.expect_p2p and v["p2p"] != 1)
                or (a.expect_no_p2p and v["p2p"] != 0)
+               or not v["const_held"]
+               or (a.const_points == "all" and v["solver_used"][0] == pkg.DAB_LINEAR_SOLVER_EXPLICIT_SCHUR
+                   and v["assembly"] != (pkg.DAB_SCHUR_DIRECT,) * 3)
                or v["solver_used"][0] != v["solver_used"][1]]
         sys.stdout.write("DIST_CHECK " + ("FAIL " + ",".join(bad) if bad else "OK") + "\n")  # one write
         sys.stdout.flush()
