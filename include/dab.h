@@ -541,7 +541,15 @@ int dab_sync(dab_handle* h);
  * observation on this rank; ug[*num_free_ext][27] (U upper-packed (21) | g_c (6) per free
  * extrinsic in ascending index, summed over the ranks); ux[*num_cross][36] (the arc-ring cross blocks);
  * *cost = 0.5 * sum r^2. Every pointer may be NULL: query the two counts first, then call
- * again with arrays of those sizes. The handle's state is unchanged. */
+ * again with arrays of those sizes. The handle's state is unchanged.
+ * Cross blocks: one per (arc, ring) = (ext0, ext1) pair that has, on some rank, a composed
+ * observation whose two extrinsics are both free. Order: ascending key col(ext0) * num_free_ext
+ * + col(ext1), col = the extrinsic's rank among the free ones (its row in ug), i.e. by arc, then
+ * by ring. Orientation: the 36 numbers are J_c0^T J_c1 row-major, ux[k][6 a + b] = sum over the
+ * pair's observations and their two residual rows of (d r / d ext0_a) (d r / d ext1_b): rows
+ * index the arc's (w, t), columns the ring's; this is the block at (row block col(ext0),
+ * column block col(ext1)) of the camera part of J^T J; the block at (col(ext1), col(ext0)) is its
+ * transpose and is not stored. */
 int dab_bench_get_blocks(dab_handle* h, int32_t* num_free_ext, int32_t* num_cross, double* V, double* g,
                          double* ug, double* ux, double* cost);
 /* Kernel timing: average device time (ms) of the point-side residual+Jacobian kernel and
