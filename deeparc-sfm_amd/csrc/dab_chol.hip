@@ -56,6 +56,9 @@ struct CholCtx {
   int ncu = 256;
   unsigned* bar = nullptr;  // grid-barrier counter of k_trsv_back_all (zeroed per solve)
   bool back_flow = true;      // DAB_CHOL_BACK_FLOW=0: the grid-barrier back substitution
+  int back_groups = 0;        // DAB_CHOL_BACK_GROUPS=g (g >= 1): at most g back-substitution work-groups, so
+                              // that small systems reach the several-blocks-per-owner and fallback paths
+                              // (debugging and tests, not tuning; 0: no cap)
   bool prefactor = true;      // DAB_CHOL_PREFACTOR=0: every panel work-group factors the diagonal block
   bool nograph = false;       // DAB_CHOL_NOGRAPH=1: launch directly instead of the captured graph (traces)
   int graph_min = 16;         // DAB_CHOL_GRAPH_MIN: fewest blocks that use the captured graph
@@ -84,6 +87,7 @@ CholCtx* chol_create() {
   if (const char* e = getenv("DAB_CHOL_STRIP")) c->strip = atoi(e) != 0;
   if (const char* e = getenv("DAB_CHOL_GROUP")) c->group = std::max(2, atoi(e));
   if (const char* e = getenv("DAB_CHOL_BACK_FLOW")) c->back_flow = atoi(e) != 0;
+  if (const char* e = getenv("DAB_CHOL_BACK_GROUPS")) c->back_groups = std::max(1, atoi(e));
   if (const char* e = getenv("DAB_CHOL_PREFACTOR")) c->prefactor = atoi(e) != 0;
   if (const char* e = getenv("DAB_CHOL_FUSE_PANEL")) c->fuse_panel = atoi(e) != 0;
   c->nograph = getenv("DAB_CHOL_NOGRAPH") != nullptr;
@@ -1205,7 +1209,7 @@ static int chol_build(CholCtx* c, hipStream_t s, int n, double* A, int lda, doub
 }
 
 static void enqueue_back_substitution(CholCtx* c, hipStream_t s, int n, double* A, int lda, double* y,
-                                      int* d_flag, bool y_filled);
+                                      int* d_flag);
 static void enqueue_factor_solve_v1(CholCtx* c, hipStream_t s, int n, double* A, int lda, double* y,
                                     int* d_flag);
 // Panel PAIRS with lookahead. Chain stream s, per pair (b, b+1): [wait the previous pair's
@@ -1298,18 +1302,19 @@ static void enqueue_factor_solve(CholCtx* c, hipStream_t s, int n, double* A, in
     panel(cend);
   }
   if (pending >= 0) (void)hipStreamWaitEvent(s, c->ev_bulk[pending], 0);
-  enqueue_back_substitution(c, s, n, A, lda, y, d_flag, true);
+  enqueue_back_substitution(c, s, n, A, lda, y, d_flag);
 }
 
-// y_filled: the factorisation's first panel launch set y to the pending pattern
+// k_trsv_back_flow polls y itself: y_b is pending until its owner stores it. The kernel relies
+// on the first k_panel launch of the same factorisation (enqueue_factor_solve's panel(0))
+// having filled y with the pending pattern; there is no fill here.
 static void enqueue_back_substitution(CholCtx* c, hipStream_t s, int n, double* A, int lda, double* y,
-                                      int* d_flag, bool y_filled) {
+                                      int* d_flag) {
   const int nblk = (n + NB - 1) / NB;
   double* z = A + (size_t)n * lda;
-  const int G = std::max(1, std::min(c->ncu / 2, (n + 63) / 64));
+  int G = std::max(1, std::min(c->ncu / 2, (n + 63) / 64));
+  if (c->back_groups > 0) G = std::min(G, c->back_groups);  // DAB_CHOL_BACK_GROUPS
   if (c->back_flow && nblk <= G * kMaxOwned) {
-    // y_b is pending until its owner stores it (k_trsv_back_flow polls the values themselves)
-    if (!y_filled) (void)hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(y), kYPending32, 2 * (size_t)n, s);
     k_trsv_back_flow<<<G, kThreads, 0, s>>>(A, lda, n, nblk, c->blk, z, y, d_flag);
     return;
   }
