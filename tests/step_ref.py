@@ -1,0 +1,632 @@
+"""TEST INFRASTRUCTURE ONLY: the reference for the direct tests of one LM linear step (a plain
+module, no GPU). tests/test_step_ref.py pins it and the conditions of every case;
+tests/test_gpu_step.py runs the device on the cases.
+
+One LM iteration (max_num_iterations = 1, function / gradient / parameter tolerance 0) exposes
+the whole linear step through the public ABI: the accepted parameters minus the initial ones are
+the step Delta. What lies between the evaluation pass and the dense Cholesky (the point factor,
+the Y records, S on its three routes, the fixed-point right-hand side, the intrinsic border, both
+back substitutions, the PCG operator and its update kernels, the candidate and model-cost pass)
+is judged on that step, block by block.
+
+The system is the damped, Jacobi-scaled normal equations of robust_ref.lm over the layout of
+ptconst_ref._Layout (which is robust_ref's without a mask and intr_ref's without constant
+points), from the oracle's rows, corrected under a loss: As = A scale,
+d = clip(sum As^2, min_lm_diagonal, max_lm_diagonal) / radius, (As^T As + diag d) y = -As^T r,
+Delta = y scale. It is kept as rows ([2 N][21] values and columns); only 3 x 3 point blocks and
+the camera (+ intrinsic) system are ever dense.
+
+Steps: System.step64() is block elimination and numpy's Cholesky of the reduced system in
+float64 (robust_ref.lm's step up to the summation order); System.refined() adds rounds of
+iterative refinement with the residual of the full system from the rows in long double, y kept in
+long double, until eta stops falling (eta_ref <= 0.01 eps is asserted for every case on the CPU).
+
+Metric (dense_ref.py's, per row, long double; H = As^T As + diag d, g = As^T r, D = sqrt(diag H)):
+  eta_i = |D^-1 (H y + g)|_i / (|D^-1 H D^-1|_inf |D y|_inf + |D^-1 g|_inf)
+with y = Delta / scale; the matrix norm is taken in float64. The formula is the same with and
+without Jacobi scaling (every factor is invariant under a diagonal scaling). block_eta() gives
+the worst eta_i of every parameter block (a point's 3, a camera's 6, an intrinsic's active
+scalars) and block_name() says which block that is.
+
+The read-back channel: Delta is observed as fl(x1 - x0) after the library formed fl(x0 + Delta),
+which loses eps |x| / |Delta|. Every yardstick passes through channel() first.
+
+Pass rule of the GPU tests, for every block of the device's step:
+  exact step  eta_dev <= K max(eta_64, eps); eta_64 is the case's yardstick, the worst eta of
+              step64() through the channel
+  PCG (eta 1e-14, 1000 iterations)  eta_dev <= K_PCG max(eta_cg, eps), eta_cg the worst eta of the
+              oracle's CG step (orc.solve, same options, one iteration; under a point mask cg()
+              below, which restates it and is pinned to it), observed through the same channel
+K and K_PCG are each one constant: four times the worst ratio measured on an MI355X over all
+cases, rounded up to a power of two, at most 64; a case that needs more is a finding about the
+kernel, not a tolerance. Measured worst eta_dev / max(eta_ref, eps) per case group (MEASURED):
+  exact   tiles 6.58 (Cauchy; no loss: 5.92)   pair tables 4.75   direct and masked 2.94
+          free intrinsics 1.16                  so K = 32 (4 x 6.58 = 26.3)
+  PCG     stored Y, fused or not, one or many CG work-groups, and matrix-free alike: 14.98 on
+          bal-small, 8.8 on rig-small, 1.00 on 161 cameras and under the mask, 2.4 near the
+          minimum                               so K_PCG = 64 (4 x 14.98 = 59.9)
+eta_dev itself is 3.5 - 6.5 eps at radius 1e4 and 1e12 on BAL shapes (eta_64 about 1 eps), 17 -
+20 eps on rig-small (4 - 12), and at radius 1e-2 the channel's 694 and 6243 eps for both. The PCG
+figure is a stopping effect and not the operator: on bal-small the device stops after 28
+iterations as cg() does (eta 1.29e4 eps for both) and the oracle after 29 (863 eps).
+Against the reference's eta of the same block instead of the case's worst (printed by the tests,
+not asserted) the worst ratios are 76 near the minimum, 17 on rig-small and 12 under Cauchy.
+That is the float64 evaluation of r and not the linear step: perturbing the oracle's r by half
+an ulp of the pixel coordinate alone, with everything after it as in step64(), gives 22 - 38, 3 -
+11 and 14 - 18 on those cases. Near a minimum g = As^T r is five orders below sum |As| |r|, so an
+ulp of r is 1e5 ulps of g.
+
+LM scalars of the iteration, long double: step_norm(), model_cost_change() (with the sum of its
+absolute terms, the scale of the project's 1e-12 bound for a cost sum) and cost().
+"""
+import functools
+import math
+
+import numpy as np
+import scipy.sparse as sp
+from scipy.linalg import cho_factor, cho_solve
+
+import intr_ref as ir
+import ptconst_ref as pr
+import robust_ref as rr
+
+LD = np.longdouble
+EPS = float(np.finfo(np.float64).eps)
+ETA_REF_MAX = 0.01 * EPS
+
+# constants of the explicit step's schedule (csrc/dab_kernels.h, dab_schur_tables.hip, dab_rows.h)
+TILE_BLOCKS, BATCH_POINTS, TILE_MAX_REC, MF_CAMS_MAX, SMALL_TABS, PAIR_CHUNK = 1024, 64, 32, 160, 128, 2560
+TILE_LDS = 163840
+
+PAIRS, TILES, DIRECT = 0, 1, 2          # DAB_SCHUR_*
+STORED_Y, MATRIX_FREE = 0, 1            # DAB_PCG_*
+
+# worst eta_dev / max(eta_ref64, eps) over the blocks of every case of a group, measured on an
+# MI355X (tests/test_gpu_step.py prints them), and the constants from them
+MEASURED = {"tiles": 6.577, "pairs": 4.751, "masked": 2.942, "intr": 1.158}
+MEASURED_PCG = {"pcg": 14.977, "masked": 1.000}
+K = 32
+K_PCG = 64
+for _k, _m in ((K, MEASURED), (K_PCG, MEASURED_PCG)):
+    assert _k <= 64 and _k >= 4 * max(_m.values()) > _k / 2
+
+
+def batch_cap(nc, single=True):
+    """schur_tile_batch_cap: records of one batch (one LDS buffer of TILE_LDS, or one of two)."""
+    hdr = (8 * nc + 4 * (nc + 1) + 15) // 16 * 16
+    area = ((TILE_LDS if single else TILE_LDS // 2) - (hdr + 1023) // 1024 * 1024) // 1024 * 1024
+    return area // 144
+
+
+# ---- the system ------------------------------------------------------------------------------
+class System:
+    """The linear system of the first LM iteration of `prob` (module docstring)."""
+
+    def __init__(self, pkg, orc, prob, radius=1e4, jacobi=1, dmin=1e-6, dmax=1e32, const=None, groups=0,
+                 loss=(rr.TRIVIAL, 1.0)):
+        self.pkg, self.orc, self.prob, self.loss = pkg, orc, prob, loss
+        L = self.L = pr._Layout(prob, const, groups)
+        n = self.n = L.n
+        r, J = orc.eval_jacobians(pkg, prob)
+        assert np.isfinite(r).all() and np.isfinite(J).all()
+        rt, Jt, ps = rr.correct(loss[0], loss[1], r, np.concatenate([J, ir.jz(prob)], axis=2))
+        self.cost0 = float(0.5 * ps.astype(LD).sum())
+        N = prob.num_obs
+        col = np.concatenate([L.col, L.zcol], axis=1)           # [N][21], -1: no column
+        val = np.where(col[:, None, :] >= 0, Jt, 0.0)            # [N][2][21]
+        self.col = np.repeat(np.where(col >= 0, col, n), 2, axis=0)  # [2 N][21], n: a dummy column
+        self.val = val.reshape(2 * N, 21)
+        self.r = rt.reshape(2 * N)
+        self.x0 = L.pack(prob)
+        colsq = np.zeros(n + 1)
+        np.add.at(colsq, self.col, self.val ** 2)
+        self.scale = 1.0 / (1.0 + np.sqrt(colsq[:n])) if jacobi else np.ones(n)
+        self.vs = self.val * np.append(self.scale, 0.0)[self.col]  # the rows of As
+        cs = np.zeros(n + 1)
+        np.add.at(cs, self.col, self.vs ** 2)
+        self.d = np.clip(cs[:n], dmin, dmax) / radius
+        self.clipped = (int((cs[:n] < dmin).sum()), int((cs[:n] > dmax).sum()))
+        # parameter blocks
+        P = self.P = 3 * L.np
+        bid = np.empty(n, np.int64)
+        bid[:P] = np.arange(P) // 3
+        bid[P:L.n_pc] = L.np + np.arange(6 * L.nc) // 6
+        zid = np.unique(L.zi, return_inverse=True)[1] if L.nz else np.zeros(0, np.int64)
+        bid[L.n_pc:] = L.np + L.nc + zid
+        self.bid, self.nblocks = bid, L.np + L.nc + (int(zid.max()) + 1 if L.nz else 0)
+        self.zblock = np.unique(L.zi) if L.nz else np.zeros(0, np.int64)
+        self._reduce()
+
+    # -- long double products over the rows
+    def _A(self, vals, x):
+        return (vals.astype(LD) * np.append(x.astype(LD), LD(0))[self.col]).sum(axis=1)
+
+    def _AT(self, vals, v):
+        out = np.zeros(self.n + 1, LD)
+        np.add.at(out, self.col, vals.astype(LD) * v.astype(LD)[:, None])
+        return out[:self.n]
+
+    @functools.cached_property
+    def g(self):
+        """g = As^T r in long double, each entry the exact sum of its float64 products rounded once
+        (Dekker's product, math.fsum). Near a minimum g is many orders below sum |As| |r|, and a
+        long-double accumulation of it would be the reference's own floor."""
+        a = np.where(self.col < self.n, self.vs, 0.0).ravel()
+        b = np.repeat(self.r, 21)
+        hi = a * b
+        sa, sb = a * 134217729.0, b * 134217729.0
+        a1, b1 = sa - (sa - a), sb - (sb - b)
+        a2, b2 = a - a1, b - b1
+        lo = a2 * b2 - (((hi - a1 * b1) - a2 * b1) - a1 * b2)
+        order = np.argsort(self.col.ravel(), kind="stable")
+        cols = self.col.ravel()[order]
+        cut = np.searchsorted(cols, np.arange(self.n + 1))
+        hi, lo = hi[order], lo[order]
+        out = np.zeros(self.n, LD)
+        for j in range(self.n):
+            parts = np.concatenate([hi[cut[j]:cut[j + 1]], lo[cut[j]:cut[j + 1]]]).tolist()
+            s1 = math.fsum(parts)
+            out[j] = LD(s1) + LD(math.fsum(parts + [-s1]))
+        return out
+
+    def residual(self, y):
+        """H y + g in long double, from the rows."""
+        return self._AT(self.vs, self._A(self.vs, y)) + self.d.astype(LD) * y.astype(LD) + self.g
+
+    # -- float64 block elimination
+    def _reduce(self):
+        n, P = self.n, self.P
+        rows = np.repeat(np.arange(self.col.shape[0]), 21)
+        keep = self.col.ravel() < n
+        As = sp.csr_matrix((self.vs.ravel()[keep], (rows[keep], self.col.ravel()[keep])), shape=(len(self.r), n))
+        H = (As.T @ As + sp.diags(self.d)).tocsr()
+        self.Hdiag = H.diagonal()
+        Dinv = 1.0 / np.sqrt(self.Hdiag)
+        self.norm = float(np.asarray(abs(sp.diags(Dinv) @ H @ sp.diags(Dinv)).sum(axis=1)).max())
+        self.g64 = As.T @ self.r
+        self.Hcc = H[P:, P:].toarray()
+        npnt = self.L.np
+        if npnt:
+            Hpp = H[:P, :P].tobsr(blocksize=(3, 3))
+            Hpp.sort_indices()
+            assert Hpp.data.shape[0] == npnt and (Hpp.indices == np.arange(npnt)).all()
+            # block Cholesky: V = L L^T per point, Y = L^-1 H_pc, S = H_cc - Y^T Y (the Cholesky
+            # factorisation of H with the points first: backward stable, unlike S from explicit V^-1)
+            Lp = np.linalg.cholesky(Hpp.data)
+            a, b, c, d, e, f = Lp[:, 0, 0], Lp[:, 1, 0], Lp[:, 1, 1], Lp[:, 2, 0], Lp[:, 2, 1], Lp[:, 2, 2]
+            Li = np.zeros_like(Lp)
+            Li[:, 0, 0], Li[:, 1, 1], Li[:, 2, 2] = 1.0 / a, 1.0 / c, 1.0 / f
+            Li[:, 1, 0] = -b * Li[:, 0, 0] / c
+            Li[:, 2, 1] = -e * Li[:, 1, 1] / f
+            Li[:, 2, 0] = -(d * Li[:, 0, 0] + e * Li[:, 1, 0]) / f
+            self.Linv = sp.bsr_matrix((Li, np.arange(npnt), np.arange(npnt + 1)), shape=(P, P))
+            self.LinvT = self.Linv.T.tocsr()
+            self.Y = (self.Linv @ H[:P, P:]).tocsr()
+            self.S = self.Hcc - (self.Y.T @ self.Y).toarray()
+        else:
+            self.S = self.Hcc
+        self.S = 0.5 * (self.S + self.S.T)
+        self._chol = cho_factor(self.S, lower=True) if n > P else None
+
+    def solve64(self, b):
+        """H^-1 b by block elimination, float64."""
+        P = self.P
+        b = np.asarray(b, np.float64)
+        if not self.L.np:
+            return cho_solve(self._chol, b)
+        t = self.Linv @ b[:P]
+        yc = cho_solve(self._chol, b[P:] - self.Y.T @ t) if self.n > P else np.zeros(0)
+        return np.concatenate([self.LinvT @ (t - self.Y @ yc), yc])
+
+    def step64(self):
+        """The float64 step Delta (robust_ref.lm's, up to the summation order)."""
+        return self.solve64(-self.g64) * self.scale
+
+    @functools.lru_cache(maxsize=None)
+    def refined(self, max_rounds=8):
+        """(Delta in long double, eta, rounds): the float64 step refined with long-double residuals
+        until eta stops falling."""
+        y = self.solve64(-self.g64).astype(LD)
+        best, e, rounds = y, self.eta_rows_y(y).max(), 0
+        for k in range(max_rounds):
+            y = y - self.solve64(self.residual(y).astype(np.float64)).astype(LD)
+            e1 = self.eta_rows_y(y).max()
+            if not e1 < e:
+                break
+            best, e, rounds = y, e1, k + 1
+        return best * self.scale.astype(LD), float(e), rounds
+
+    # -- the metric
+    def eta_rows_y(self, y):
+        D = np.sqrt(self.Hdiag.astype(LD))
+        g = self.g
+        den = LD(self.norm) * np.abs(D * y).max() + np.abs(g / D).max()
+        return np.abs(self.residual(y) / D) / den
+
+    def eta_rows(self, delta):
+        """eta_i of a step Delta given in the parameters' own units."""
+        if not np.isfinite(np.asarray(delta, np.float64)).all():
+            return np.full(self.n, np.inf)
+        return self.eta_rows_y(np.asarray(delta, LD) / self.scale.astype(LD))
+
+    def block_eta(self, delta):
+        """[nblocks] the worst eta_i of every parameter block, float64."""
+        out = np.zeros(self.nblocks)
+        np.maximum.at(out, self.bid, self.eta_rows(delta).astype(np.float64))
+        return out
+
+    def block_name(self, b):
+        L = self.L
+        if b < L.np:
+            return f"point {L.pt_of[b]}"
+        if b < L.np + L.nc:
+            return f"extrinsic {L.ext_of[b - L.np]} (free camera {b - L.np})"
+        return f"intrinsic {self.zblock[b - L.np - L.nc]}"
+
+    def camera_blocks(self, cams):
+        """block ids of free cameras `cams` (positions in the free order)."""
+        return self.L.np + np.asarray(cams)
+
+    # -- the channel and the scalars
+    def channel(self, delta):
+        """What reading x1 - x0 back shows of Delta: fl(fl(x0 + Delta) - x0)."""
+        return (self.x0 + np.asarray(delta, np.float64)) - self.x0
+
+    def observed(self, after):
+        """The step of a solved problem `after` that started from this system's problem."""
+        return self.L.pack(after) - self.x0
+
+    def step_norm(self, delta):
+        return float(np.sqrt((np.asarray(delta, LD) ** 2).sum()))
+
+    def model_cost_change(self, delta):
+        """(-sum m (r + m / 2), sum |m (r + m / 2)|) with m = A Delta, long double."""
+        m = self._A(self.val, np.asarray(delta, LD))
+        t = m * (self.r.astype(LD) + m / 2)
+        return float(-t.sum()), float(np.abs(t).sum())
+
+    def cost(self, delta=None, prob=None):
+        """0.5 sum rho at x0 + Delta (or at the parameters of `prob`), summed in long double."""
+        if prob is None:
+            prob = self.prob.copy()
+            self.L.unpack(self.x0 + np.asarray(delta, np.float64), prob)
+        r, _ = self.orc.eval_residuals(self.pkg, prob)
+        if not np.isfinite(r).all():
+            return rr.DBL_MAX
+        s = (r.astype(LD) ** 2).sum(axis=1)
+        if self.loss[0] == rr.TRIVIAL:
+            return float(0.5 * s.sum())
+        return float(0.5 * rr.rho(self.loss[0], self.loss[1], s.astype(np.float64))[0].astype(LD).sum())
+
+    def relative_decrease(self, delta):
+        """(cost0 - cost(x0 + Delta)) / model_cost_change(Delta): > min_relative_decrease = accepted."""
+        mc = self.model_cost_change(delta)[0]
+        return (self.cost0 - self.cost(delta)) / mc if mc > 0 else -np.inf
+
+    # -- the oracle's CG, restated (oracle/dab_oracle.c, cg_solve), on this system's S
+    def cg(self, eta=1e-14, max_it=1000, min_it=0):
+        """(Delta, iterations) of the block-Jacobi preconditioned CG step: cameras by CG on S, points
+        by back substitution. Only for layouts without free intrinsics (6 x 6 blocks)."""
+        assert self.L.nz == 0
+        P, S = self.P, self.S
+        gp, gc = -self.g64[:P], -self.g64[P:]
+        t = self.Linv @ gp if self.L.np else gp
+        b = gc - self.Y.T @ t if self.L.np else gc
+        ns, nc = len(b), len(b) // 6
+        Minv = np.linalg.inv(np.stack([S[6 * c:6 * c + 6, 6 * c:6 * c + 6] for c in range(nc)]))
+        x, r, p = np.zeros(ns), b.copy(), np.zeros(ns)
+        rho = Q0 = 0.0
+        it = 0
+        if (b * b).sum() != 0.0:
+            for it in range(1, max_it + 1):
+                z = np.einsum("cab,cb->ca", Minv, r.reshape(nc, 6)).ravel()
+                rho_new = r @ z
+                p = z if it == 1 else z + (rho_new / rho) * p
+                rho = rho_new
+                q = S @ p
+                pq = p @ q
+                if pq <= 0.0:
+                    break
+                alpha = rho / pq
+                x = x + alpha * p
+                r = b - S @ x if it % 10 == 0 else r - alpha * q
+                Q1 = -(x @ (b + r))
+                if it * (Q1 - Q0) / Q1 < eta and it >= min_it:
+                    break
+                Q0 = Q1
+        yp = self.LinvT @ (t - self.Y @ x) if self.L.np else np.zeros(0)
+        return np.concatenate([yp, x]) * self.scale, it
+
+
+# ---- schedule facts that depend only on the problem ---------------------------------------------
+def free_cameras_per_point(prob, const=None):
+    """[referenced free points] the number of distinct free cameras that see each, in id order."""
+    L = pr._Layout(prob, const, 0)
+    cam = (L.col[:, [3, 9]] - 3 * L.np) // 6           # free-camera position or negative
+    cam = np.where(L.col[:, [3, 9]] >= 0, cam, -1)
+    pt = L.col[:, 0] // 3
+    ok = (L.col[:, 0] >= 0)[:, None] & (cam >= 0)
+    pairs = np.unique(np.stack([np.repeat(pt, 2)[ok.ravel()], cam.ravel()[ok.ravel()]], axis=1), axis=0)
+    return np.bincount(pairs[:, 0], minlength=L.np), pairs
+
+
+def shared_points(prob, const=None):
+    """[nc][nc] the number of free points that two free cameras both see."""
+    L = pr._Layout(prob, const, 0)
+    _, pairs = free_cameras_per_point(prob, const)
+    M = sp.csr_matrix((np.ones(len(pairs)), (pairs[:, 0], pairs[:, 1])), shape=(max(L.np, 1), L.nc))
+    return np.asarray((M.T @ M).todense()).astype(np.int64)
+
+
+def first_batch_points(prob, single=True):
+    """Points of the first batch of the tile route (cut_batches of dab_schur_tables.hip)."""
+    m, _ = free_cameras_per_point(prob)
+    cap = batch_cap(pr._Layout(prob).nc, single)
+    cur = 0
+    for p, k in enumerate(m):
+        if p > 0 and (cur + k > cap or p + 1 > BATCH_POINTS):
+            return p
+        cur += k
+    return len(m)
+
+
+# ---- the problems --------------------------------------------------------------------------------
+TRIVIAL = (rr.TRIVIAL, 1.0)
+
+
+def _bal(pkg, ncam, npt, opp, seed):
+    return pkg.synth(kind=0, num_cameras=ncam, num_points=npt, obs_per_point=opp, seed=seed)
+
+
+def _rank_in_track(prob):
+    order = np.argsort(prob.obs_point, kind="stable")
+    pts = prob.obs_point[order]
+    first = np.r_[0, np.flatnonzero(np.diff(pts)) + 1]
+    start = np.repeat(first, np.diff(np.r_[first, len(pts)]))
+    rank = np.zeros(prob.num_obs, np.int64)
+    rank[order] = np.arange(len(pts)) - start
+    return rank
+
+
+def _one_long_track(pkg, nfree_seen, seed):
+    """40 cameras (39 free), 200 points seen by 4 cameras each, and point 5 seen by exactly
+    `nfree_seen` distinct free cameras."""
+    base = _bal(pkg, 40, 200, 38, seed)
+    keep = _rank_in_track(base) < 4
+    of5 = np.flatnonzero((base.obs_point == 5) & (base.ext_const[base.obs_ext0] == 0))
+    keep[base.obs_point == 5] = False
+    keep[of5[:nfree_seen]] = True
+    return base.subset(keep).copy()
+
+
+def p_bal_small(pkg, orc):
+    return rr.bal_small(pkg, orc, contaminated=False)[0], None, 0, TRIVIAL
+
+
+def p_rig_small(pkg, orc):
+    return rr.rig_small(pkg, orc, contaminated=False)[0], None, 0, TRIVIAL
+
+
+def p_bal46(pkg, orc):
+    return _bal(pkg, 47, 300, 6, 201), None, 0, TRIVIAL
+
+
+def p_bal111(pkg, orc):
+    return _bal(pkg, 112, 300, 6, 202), None, 0, TRIVIAL
+
+
+def p_bal127(pkg, orc):
+    return _bal(pkg, 128, 300, 6, 209), None, 0, TRIVIAL
+
+
+def p_bal128(pkg, orc):
+    return _bal(pkg, 129, 300, 6, 210), None, 0, TRIVIAL
+
+
+def p_bal160(pkg, orc):
+    return _bal(pkg, 161, 400, 6, 203), None, 0, TRIVIAL
+
+
+def p_bal161(pkg, orc):
+    return _bal(pkg, 162, 400, 6, 204), None, 0, TRIVIAL
+
+
+def p_rec32(pkg, orc):
+    return _one_long_track(pkg, 32, 205), None, 0, TRIVIAL
+
+
+def p_rec33(pkg, orc):
+    return _one_long_track(pkg, 33, 205), None, 0, TRIVIAL
+
+
+def p_tracks20(pkg, orc):
+    return _bal(pkg, 24, 150, 20, 206), None, 0, TRIVIAL
+
+
+def p_tracks10(pkg, orc):
+    return _bal(pkg, 24, 150, 10, 207), None, 0, TRIVIAL
+
+
+def p_bal_1e8(pkg, orc):
+    prob = p_bal_small(pkg, orc)[0]
+    prob.intr[:, :4] *= 1e8
+    prob.obs_xy *= 1e8
+    return prob, None, 0, TRIVIAL
+
+
+def p_near_min(pkg, orc):
+    prob = p_bal_small(pkg, orc)[0]
+    s = rr.lm(pkg, orc, prob, pkg.options(max_num_iterations=15, num_threads=4))
+    # Given 15 iterations the reference stops at its default function tolerance after two (bal-small
+    # converges quadratically): gradient 1.7 against 1.3e5 at the start. Fifteen iterations with
+    # the tolerances off end at float64's floor (step 7e-12, cost changes below eps cost), where
+    # the reference's own next step is rejected (relative decrease -1.9e5): nothing to observe.
+    assert s["termination"] == "CONVERGENCE" and 2 <= s["num_iterations"] < 15, s["message"]
+    return prob, None, 0, TRIVIAL
+
+
+def p_cauchy(pkg, orc):
+    return rr.bal_small(pkg, orc, contaminated=True)[0], None, 0, (rr.CAUCHY, 0.5)
+
+
+def p_rig_large(pkg, orc):
+    return (pkg.synth(kind=1, num_arcs=9, num_rings=122, num_points=2500, obs_per_point=6, seed=23), None, 0,
+            TRIVIAL)
+
+
+def p_pair2600(pkg, orc):
+    return _bal(pkg, 3, 2600, 3, 208), None, 0, TRIVIAL
+
+
+def p_bal_holes(pkg, orc):
+    prob = _bal(pkg, 20, 150, 4, 104)
+    return prob.subset((prob.obs_point != 7) & (prob.obs_ext0 != 3)).copy(), None, 0, TRIVIAL
+
+
+def p_all_const(pkg, orc):
+    prob = p_bal_small(pkg, orc)[0]
+    return prob, pr.all_points(prob), 0, TRIVIAL
+
+
+def p_third_const(pkg, orc):
+    prob = p_bal_small(pkg, orc)[0]
+    return prob, pr.every_third(prob), 0, TRIVIAL
+
+
+def p_rig_third_const(pkg, orc):
+    """The masked PCG case: on bal-small with every third point constant the oracle's CG needs 15
+    iterations, on rig-small 23 (both residual resets run)."""
+    prob = p_rig_small(pkg, orc)[0]
+    return prob, pr.every_third(prob), 0, TRIVIAL
+
+
+def p_shape_a(pkg, orc):
+    return ir.shape_a(pkg, orc), None, 7, TRIVIAL
+
+
+def p_shape_b(pkg, orc):
+    return ir.shape_b(pkg, orc), None, 7, TRIVIAL
+
+
+PROBLEMS = {f.__name__[2:]: f for f in (
+    p_bal_small, p_rig_small, p_bal46, p_bal111, p_bal127, p_bal128, p_bal160, p_bal161, p_rec32, p_rec33, p_tracks20, p_tracks10,
+    p_bal_1e8, p_near_min, p_cauchy, p_rig_large, p_pair2600, p_bal_holes, p_all_const, p_third_const, p_rig_third_const, p_shape_a,
+    p_shape_b)}
+
+
+# ---- the cases -----------------------------------------------------------------------------------
+class Case:
+    """One GPU case: a problem, the options and knobs of its one iteration, the schedule it names.
+    facts: nc (free cameras), maxrec (most distinct free cameras of a point), chunk (a pair shares
+    more than PAIR_CHUNK points), holes (a pair of free cameras shares no point), big_tabs (E > 128),
+    cut (the first batch is cut by the record cap before 64 points)."""
+
+    def __init__(self, group, problem, radius=1e4, jacobi=1, clip=None, env=None, pcg=False, assembly=TILES,
+                 **facts):
+        self.group, self.problem, self.radius, self.jacobi, self.clip = group, problem, radius, jacobi, clip
+        self.env, self.pcg, self.assembly, self.facts = dict(env or {}), pcg, assembly, facts
+        bits = [group, problem, f"r{radius:g}", f"j{jacobi}"] + [f"{k[4:]}={v}" for k, v in self.env.items()]
+        self.id = "-".join(bits + ([f"clip{clip[0]:g}_{clip[1]:g}"] if clip else []))
+
+    @property
+    def key(self):
+        """What fixes the reference system (not the knobs)."""
+        return (self.problem, self.radius, self.jacobi, self.clip)
+
+    def options(self, pkg):
+        kw = dict(max_num_iterations=1, function_tolerance=0.0, gradient_tolerance=0.0, parameter_tolerance=0.0,
+                  num_threads=4, initial_trust_region_radius=self.radius, jacobi_scaling=self.jacobi,
+                  linear_solver_type=pkg.DAB_LINEAR_SOLVER_EXPLICIT_SCHUR)
+        if self.clip:
+            kw.update(min_lm_diagonal=self.clip[0], max_lm_diagonal=self.clip[1])
+        if self.pcg:
+            kw.update(linear_solver_type=pkg.DAB_LINEAR_SOLVER_IMPLICIT_SCHUR_PCG, eta=1e-14,
+                      max_linear_solver_iterations=1000)
+        return pkg.options(**kw)
+
+
+def _cases():
+    out = []
+    T0 = {"DAB_SCHUR_TILES": "0"}
+    # exact step, tiles
+    for prob, radii in (("bal_small", (1e4, 1e-2, 1e12)), ("rig_small", (1e4, 1e-2, 1e12)), ("bal46", (1e4,))):
+        for radius in radii:
+            for j in (1, 0):
+                out.append(Case("tiles", prob, radius, j, **({"nc": 46} if prob == "bal46" else {})))
+    for env in ({"DAB_TILE_BALANCE": "0"}, {"DAB_TILE_SINGLE": "0"}, {"DAB_TILE_MINB": "1"}, {"DAB_TILE_MINB": "8"}):
+        out.append(Case("tiles", "bal46", env=env, nc=46))
+    out.append(Case("tiles", "bal111", nc=111))
+    # NC <= 160 (kMfCamsMax) never decides: the tables must fit LDS first (num_ext, num_intr <= 128,
+    # small_tabs_fit) and NC < num_ext. The edge that exists is 127 free cameras of 128 (eight tiles)
+    # against 128 of 129 (pair tables); 160 and 161 free cameras are both on the pair tables.
+    out.append(Case("tiles", "bal127", nc=127))
+    out.append(Case("tiles", "rec32", nc=39, maxrec=32))
+    out.append(Case("tiles", "tracks20", nc=23, cut=True))
+    out.append(Case("tiles", "tracks10", env={"DAB_TILE_SINGLE": "0"}, nc=23, cut=False))
+    # The clip. With Jacobi scaling a column's sum is (|a| / (1 + |a|))^2, here 0.989 .. 0.9997
+    # (pixels per unit of a parameter: |a| >= 94), and without it 3.5e4 .. 5.8e7: 0.5 / 0.9 clips
+    # every column from above (a uniform damping 0.9 / radius) and none from below. 0.998 / 0.999
+    # straddles the scaled sums' median 0.9985: both clips act and some columns keep their own sum.
+    out.append(Case("tiles", "bal_small", clip=(0.5, 0.9)))
+    out.append(Case("tiles", "bal_small", jacobi=0, clip=(0.5, 0.9)))
+    out.append(Case("tiles", "bal_small", clip=(0.998, 0.999), both_clips=True))
+    out.append(Case("tiles", "bal_1e8"))
+    out.append(Case("tiles", "near_min"))
+    out.append(Case("tiles", "cauchy"))
+    # exact step, pair tables
+    for prob in ("bal_small", "rig_small", "bal46"):
+        for j in (1, 0):
+            out.append(Case("pairs", prob, jacobi=j, env=T0, assembly=PAIRS))
+    out.append(Case("pairs", "bal128", assembly=PAIRS, nc=128))
+    out.append(Case("pairs", "bal160", assembly=PAIRS, nc=160))
+    out.append(Case("pairs", "bal161", assembly=PAIRS, nc=161))
+    out.append(Case("pairs", "rec33", assembly=PAIRS, nc=39, maxrec=33))
+    out.append(Case("pairs", "rig_large", assembly=PAIRS, big_tabs=True))
+    out.append(Case("pairs", "pair2600", env=T0, assembly=PAIRS, nc=2, chunk=True))
+    out.append(Case("pairs", "bal_holes", env=T0, assembly=PAIRS, holes=True))
+    # direct and masked
+    out.append(Case("masked", "all_const", assembly=DIRECT))
+    out.append(Case("masked", "third_const"))
+    out.append(Case("masked", "rig_third_const"))
+    out.append(Case("masked", "rig_third_const", pcg=True, assembly=MATRIX_FREE))
+    # free intrinsics
+    out.append(Case("intr", "shape_a"))
+    out.append(Case("intr", "shape_a", env={"DAB_INTR_BORDER_LDS": "0"}))
+    out.append(Case("intr", "shape_b"))
+    # PCG, converged
+    for prob in ("bal_small", "rig_small"):
+        out.append(Case("pcg", prob, pcg=True, assembly=MATRIX_FREE))
+        for fused, onewg in (("1", "0"), ("0", "0"), ("1", "1"), ("0", "1")):
+            out.append(Case("pcg", prob, pcg=True, assembly=STORED_Y,
+                            env={"DAB_PCG_MF": "0", "DAB_PCG_FUSED": fused, "DAB_CG_ONEWG": onewg}))
+    out.append(Case("pcg", "bal161", pcg=True, assembly=STORED_Y, nc=161))
+    out.append(Case("pcg", "near_min", pcg=True, assembly=MATRIX_FREE))
+    ids = [c.id + ("-pcg" if c.pcg and c.group != "pcg" else "") for c in out]
+    assert len(set(ids)) == len(ids)
+    for c, i in zip(out, ids):
+        c.id = i
+    return out
+
+
+CASES = _cases()
+KNOBS = ("DAB_SCHUR_TILES", "DAB_TILE_BALANCE", "DAB_TILE_SINGLE", "DAB_TILE_MINB", "DAB_PCG_MF", "DAB_PCG_FUSED",
+         "DAB_CG_ONEWG", "DAB_INTR_BORDER_LDS", "DAB_POINTS_DIRECT", "DAB_SETUP_HOST", "DAB_XCHUNK")
+
+_problems, _systems = {}, {}
+
+
+def problem(pkg, orc, name):
+    """(start problem, constant-point mask or None, intrinsic groups, loss), built once; copy before use."""
+    if name not in _problems:
+        _problems[name] = PROBLEMS[name](pkg, orc)
+    return _problems[name]
+
+
+def system(pkg, orc, case):
+    """The System of a case, built once per (problem, radius, jacobi, clip) and never modified."""
+    if case.key not in _systems:
+        prob, const, groups, loss = problem(pkg, orc, case.problem)
+        clip = case.clip or (1e-6, 1e32)
+        _systems[case.key] = System(pkg, orc, prob.copy(), case.radius, case.jacobi, clip[0], clip[1], const, groups,
+                                    loss)
+    return _systems[case.key]
