@@ -163,6 +163,9 @@ SIGNATURES = {
     "dab_get_intrinsics_free": (C.c_int, [C.c_void_p, _u8p, _ip, _ip]),
     "dab_set_points_constant": (C.c_int, [C.c_void_p, _u8p]),
     "dab_get_points_constant": (C.c_int, [C.c_void_p, _u8p, _ip]),
+    "dab_set_ext_priors": (C.c_int, [C.c_void_p, C.c_int32, _ip, _dp, _dp]),
+    "dab_get_ext_priors": (C.c_int, [C.c_void_p, _ip, _ip, _ip, _dp, _dp]),
+    "dab_eval_ext_priors": (C.c_int, [C.c_void_p, _dp, _dp]),
     "dab_get_intrinsics": (C.c_int, [C.c_void_p, _dp]),
     "dab_update_intrinsics": (C.c_int, [C.c_void_p, _dp]),
     "dab_eval_intrinsic_jacobians": (C.c_int, [C.c_void_p, _dp]),

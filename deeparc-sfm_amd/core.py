@@ -320,6 +320,45 @@ class Solver:
         check(self.lib.dab_get_points_constant(self.h, _ptr(m, C.c_uint8), C.byref(n)), self.lib)
         return m, n.value
 
+    def set_ext_priors(self, index, mean=None, sqrt_info=None):
+        """Gaussian priors on extrinsics (dab_set_ext_priors; Ceres' NormalPrior(A, mu) with a NULL
+        loss on the extrinsic's block): index [n] extrinsic indices, mean [n][6] in the library's
+        (w, t), sqrt_info [n][6][6] = A of the residual A (x - mean). None or an empty index
+        clears them. Set after set_problem, which resets them; they survive update_parameters,
+        set_loss and the masks. A prior on a constant or unreferenced extrinsic is ignored."""
+        if index is None or np.size(index) == 0:
+            check(self.lib.dab_set_ext_priors(self.h, 0, None, None, None), self.lib)
+            return
+        idx = np.ascontiguousarray(index, np.int32).reshape(-1)
+        n = idx.shape[0]
+        mu = np.ascontiguousarray(mean, np.float64)
+        a = np.ascontiguousarray(sqrt_info, np.float64)
+        if mu.shape != (n, 6) or a.shape != (n, 6, 6):
+            raise ValueError(f"mean: ({n}, 6) and sqrt_info: ({n}, 6, 6) values")
+        check(self.lib.dab_set_ext_priors(self.h, n, _ptr(idx, C.c_int32), _ptr(mu, C.c_double),
+                                          _ptr(a, C.c_double)), self.lib)
+
+    def get_ext_priors(self):
+        """(index [n], mean [n][6], sqrt_info [n][6][6], num_effective) as set."""
+        n, ne = C.c_int32(), C.c_int32()
+        check(self.lib.dab_get_ext_priors(self.h, C.byref(n), C.byref(ne), None, None, None), self.lib)
+        idx = np.zeros(n.value, np.int32)
+        mu = np.zeros((n.value, 6))
+        a = np.zeros((n.value, 6, 6))
+        check(self.lib.dab_get_ext_priors(self.h, None, None, _ptr(idx, C.c_int32), _ptr(mu, C.c_double),
+                                          _ptr(a, C.c_double)), self.lib)
+        return idx, mu, a, ne.value
+
+    def eval_ext_priors(self):
+        """(residuals [n][6] in the order set, cost = 0.5 sum |r|^2 over the effective priors) at
+        the parameters on the handle (dab_eval_ext_priors); an ignored prior's row is zero."""
+        n = C.c_int32()
+        check(self.lib.dab_get_ext_priors(self.h, C.byref(n), None, None, None, None), self.lib)
+        r = np.zeros((n.value, 6))
+        cost = C.c_double()
+        check(self.lib.dab_eval_ext_priors(self.h, _ptr(r, C.c_double), C.byref(cost)), self.lib)
+        return r, cost.value
+
     def get_intrinsics(self):
         """The intrinsics on the handle, [num_intr][6] (refined ones after a solve)."""
         k = np.zeros((int(self.problem.intr.shape[0]), 6))
@@ -548,8 +587,18 @@ class Solver:
         return f.value  # 0 two kernels, 1 one fused launch, 2 fused kernel split per side
 
 
+def sqrt_info_from_sigmas(sigma_w, sigma_t, n=None):
+    """sqrt_info of independent priors: diag(1 / sigma_w x3, 1 / sigma_t x3), one 6x6 or [n] of
+    them. np.inf (or None) as a sigma gives zero rows: sqrt_info_from_sigmas(None, 0.01) is a
+    position-only prior."""
+    def inv(sg):
+        return 0.0 if sg is None or np.isinf(sg) else 1.0 / float(sg)
+    a = np.diag([inv(sigma_w)] * 3 + [inv(sigma_t)] * 3)
+    return a if n is None else np.repeat(a[None], int(n), axis=0)
+
+
 def solve(problem, max_iteration=1000, max_second=3600, freeze_camera=False, device=0,
-          verbose=False, loss=None, free_intrinsics=0, freeze_points=False, **opt_kw):
+          verbose=False, loss=None, free_intrinsics=0, freeze_points=False, ext_priors=None, **opt_kw):
     """Drop-in for the reference's solve() (src/sfm.cc:31): DENSE_SCHUR-equivalent LM,
     max_num_iterations / max_solver_time_in_seconds as given, parameters updated in place.
     loss: None (the reference's NULL loss, sfm.cc:48) or a (kind, scale) pair such as
@@ -558,7 +607,9 @@ def solve(problem, max_iteration=1000, max_second=3600, freeze_camera=False, dev
     equivalent of deleting sfm.cc:60-62; problem.intr is updated in place.
     freeze_points: True (every point) or a mask of num_points: the points held constant, the
     `SetParameterBlockConstant(parameter_block[0]); //freeze point3d` the reference keeps
-    commented out at sfm.cc:59 (pose-only refinement, ground-control points)."""
+    commented out at sfm.cc:59 (pose-only refinement, ground-control points).
+    ext_priors: None or (index, mean, sqrt_info), Gaussian priors on extrinsics
+    (Solver.set_ext_priors; sqrt_info_from_sigmas builds the diagonal case)."""
     problem.freeze_camera = bool(freeze_camera)
     o = options(max_num_iterations=max_iteration, max_solver_time_in_seconds=float(max_second),
                 minimizer_progress_to_stdout=int(verbose), **opt_kw)
@@ -571,6 +622,8 @@ def solve(problem, max_iteration=1000, max_second=3600, freeze_camera=False, dev
             s.set_intrinsics_free(free_intrinsics)
         if np.any(np.asarray(freeze_points)):
             s.set_points_constant(freeze_points)
+        if ext_priors is not None:
+            s.set_ext_priors(*ext_priors)
         return s.solve(o)
     finally:
         s.close()

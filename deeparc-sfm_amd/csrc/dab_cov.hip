@@ -597,6 +597,7 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
   // constant points: PU = 0 and q = 0 take them out of S and of the fold-back (their rows of
   // point_cov come out exactly 0), and the rank test leaves them out
   CHECK_RC(pt_const_sync(h));
+  CHECK_RC(prior_sync(h));  // extrinsic priors: eval_jacobian_and_blocks folds them into U | g_c
   const int nfree_pts = h->NP - h->n_pt_const;
   hipStream_t s = h->stream;
   const DevView& v = h->view;
@@ -614,7 +615,7 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
   out.num_free_points = nfree_pts;
   out.first_deficient_point = -1;
   out.schur_assembly = h->schur_tiles ? DAB_SCHUR_TILES : DAB_SCHUR_PAIRS;
-  out.num_residuals = 2 * h->N;
+  out.num_residuals = 2 * h->N + 6 * h->n_prior;
   out.num_parameters = 3 * nfree_pts + 6 * NC + cs.nz_scal;
   out.point_pivot_ratio_min = out.camera_pivot_ratio = std::numeric_limits<double>::quiet_NaN();
   for (hipEvent_t& e : h->cov_ev)
@@ -637,8 +638,8 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
   CHECK_RC(read_scalars(h));
   if (h->h_scal[S_COST_BAD] != 0.0)
     return set_error(DAB_E_INVALID, "residuals are not finite at the current parameters");
-  const double x_cost = 0.5 * h->h_scal[S_COST];
-  out.cost = x_cost;
+  const double x_cost = 0.5 * h->h_scal[S_COST];  // the observations' (bounds the tile assembly's rhs)
+  out.cost = h->n_prior > 0 ? x_cost + prior_cost(h) : x_cost;
 
   // ---- point factor without LM diagonal, and the point-side rank test ----
   dab_options lm;

@@ -162,6 +162,7 @@ enum Slot {
   // integer part, fraction * 2^52, non-finite count per shard; cost_fx_add)
   S_CFX = 16,  // two sets of kFxWords, alternating between passes
   S_XERR = S_CFX + 2 * kFxWords,  // k_eval_bal's error word (uint32 bits; 0 = ok)
+  S_PRIOR,  // 0.5 sum |A (x - mu)|^2 over the effective extrinsic priors at x (k_prior_blocks)
   S_NSLOTS
 };
 
@@ -361,6 +362,15 @@ struct Handle {
   bool pt_const_dirty = false;            // lz.d_pt_const does not hold pt_const
   const uint8_t* d_ptc = nullptr;         // [NP] device point order (lz.d_pt_const), or null
   int n_pt_const = 0;                     // constant points of this rank (of the last sync)
+  // extrinsic priors (dab_set_ext_priors), as set: state of the handle, reset by dab_set_problem.
+  // prior_sync works out the effective set (the extrinsic has a camera column) at each call that
+  // honours it and leaves its device records in lz.d_prior_*; n_prior = 0 while the set is empty,
+  // so that no prior kernel is launched then.
+  std::vector<int> prior_idx;             // [count]
+  std::vector<double> prior_mean;         // [count][6]
+  std::vector<double> prior_A;            // [count][6][6] row-major
+  bool prior_dirty = false;               // lz.d_prior_* do not hold the effective set
+  int n_prior = 0;                        // effective priors (of the last sync)
   int ldz = 0;
   // Buffers allocated from `dev` by the first call that needs them (null / capacity 0: not yet).
   // They die with dev.release(): dab_set_problem resets this whole sub-object there, so a member
@@ -379,6 +389,13 @@ struct Handle {
     int* d_ptmask = nullptr;  // [NP] free intrinsics each point sees (k_intr_ptmask, per solve)
     uint8_t* d_pt_const = nullptr;  // [NP] constant points, device point order (pt_const_sync)
     double* d_zero6 = nullptr;      // [6 NC] zeros: the rhs part of a step without free points
+    // effective extrinsic priors (prior_sync): (extrinsic, camera column) and kPriorRec doubles each
+    int2* d_prior_idx = nullptr;
+    double* d_prior_rec = nullptr;
+    double* d_prior_res = nullptr;  // [n][6] + cost: dab_eval_ext_priors
+    double* d_prior_part = nullptr;  // [2 n] per-prior terms of k_prior_blocks / k_prior_candidate
+    unsigned* d_prior_cnt = nullptr; // their arrival count (zero between launches)
+    int prior_cap = 0;
     size_t bpart_cap = 0, Sz_cap = 0;
     // dab_covariance: Z = L^-1 [n][lds], the point blocks [NP][6], the extrinsic blocks [NC][21],
     // the rank test's scalars and partials
@@ -649,6 +666,12 @@ int intr_eval(dab_handle* h);
 // ---- dab_problem.hip: constant points ----
 // the constant set of the mask on the handle -> h->d_ptc / h->n_pt_const (uploaded when changed)
 int pt_const_sync(dab_handle* h);
+
+// ---- dab_problem.hip: extrinsic priors ----
+// the effective set of the priors on the handle -> lz.d_prior_* / h->n_prior (uploaded when changed)
+int prior_sync(dab_handle* h);
+// 0.5 sum |r|^2 of the effective priors as the last evaluation left it in h_scal (0 without any)
+inline double prior_cost(const Handle* h) { return h->n_prior > 0 ? h->h_scal[S_PRIOR] : 0.0; }
 
 // ---- dab_schur_tables.hip: tables and buffers of the linear solvers, built on first use ----
 int build_schur_tables(dab_handle* h);

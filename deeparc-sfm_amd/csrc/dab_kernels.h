@@ -328,6 +328,25 @@ void launch_cov_point_rank_m(hipStream_t s, int NP, const double* V, const doubl
 void launch_cam_block_solve(hipStream_t s, int NC, const double* ug, const double* scale_c, StepScalars sc,
                             double* yc, int* fail);
 
+// ---- extrinsic priors (dab_set_ext_priors; dab_k_prior.hip) ---------------------------------
+// The n effective priors, in the order they were set: idx[i] = (extrinsic, camera column) and
+// rec[i][kPriorRec] = mean (6) | A row-major (36) | A^T A upper-packed as ug packs U (21).
+// r = A (x - mean), x = ext[extrinsic]. Every camera slot has one owner lane and every sum a fixed
+// order (no floating-point atomics). Launched only for n > 0, once per pass on every rank, after
+// the pass's sums over the ranks (extrinsics are replicated: the prior counts once). part[2 n]:
+// per-prior terms, summed by the last work-group to arrive; *cnt: its arrival count, zero between
+// launches.
+constexpr int kPriorRec = 63;
+// ug[column] += A^T A | A^T r; *cost = 0.5 sum |r|^2
+void launch_prior_blocks(hipStream_t s, int n, const int2* idx, const double* rec, const double* ext, double* ug,
+                         double* part, unsigned* cnt, double* cost);
+// model[0] += -sum m.(r + m/2), m = A delta_c[column]; model[1] += sum |A (ext_c - mean)|^2;
+// model[2] += 1 when that sum is not finite (model = d_scal + S_MODEL after the candidate pass)
+void launch_prior_candidate(hipStream_t s, int n, const int2* idx, const double* rec, const double* ext,
+                            const double* ext_c, const double* delta_c, double* part, unsigned* cnt, double* model);
+// res[i][6] = r of prior i, res[6 n] = 0.5 sum |r|^2 in prior order
+void launch_prior_eval(hipStream_t s, int n, const int2* idx, const double* rec, const double* ext, double* res);
+
 // ---- free intrinsics in the exact Schur step (dab_set_intrinsics_free; dab_k_intr.hip) -----
 // meta[NI]: x = free intrinsic index or -1; y = active columns (bits 0..5: cx cy f0 f1 k0 k1
 // selected by the mask and present in the model) | columns present in the model << 8 |

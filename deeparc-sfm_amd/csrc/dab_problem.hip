@@ -1321,6 +1321,134 @@ extern "C" int dab_get_points_constant(dab_handle* h, uint8_t* mask, int32_t* nu
   return 0;
 }
 
+// ------------------------------------------------------------------------------------
+// extrinsic priors: host state
+// ------------------------------------------------------------------------------------
+// The effective set of the priors on the handle (the extrinsic has a camera column: referenced on
+// some rank, not constant, no freeze_camera), in the order set, as device records for the calls
+// that honour it. Empty: n_prior stays 0 and nothing touches the device.
+int dab::prior_sync(dab_handle* h) {
+  h->n_prior = 0;
+  std::vector<int2> idx;
+  for (size_t i = 0; i < h->prior_idx.size(); ++i) {
+    const int e = h->prior_idx[i];
+    if (h->ext_col[(size_t)e] >= 0) idx.push_back(make_int2(e, h->ext_col[(size_t)e]));
+  }
+  const int n = (int)idx.size();
+  if (n == 0) return 0;
+  if (n > h->lz.prior_cap) {
+    h->dev.drop(h->lz.d_prior_idx);
+    h->dev.drop(h->lz.d_prior_rec);
+    h->dev.drop(h->lz.d_prior_res);
+    h->dev.drop(h->lz.d_prior_part);
+    h->lz.d_prior_idx = nullptr;
+    h->lz.d_prior_rec = h->lz.d_prior_res = h->lz.d_prior_part = nullptr;
+    h->lz.prior_cap = 0;
+    CHECK_RC(h->dev.alloc(&h->lz.d_prior_idx, (size_t)n));
+    CHECK_RC(h->dev.alloc(&h->lz.d_prior_rec, (size_t)kPriorRec * n));
+    CHECK_RC(h->dev.alloc(&h->lz.d_prior_res, (size_t)6 * n + 1));
+    CHECK_RC(h->dev.alloc(&h->lz.d_prior_part, (size_t)2 * n));
+    if (!h->lz.d_prior_cnt) CHECK_RC(h->dev.alloc(&h->lz.d_prior_cnt, (size_t)2));
+    h->lz.prior_cap = n;
+    h->prior_dirty = true;
+  }
+  if (h->prior_dirty) {
+    // mean | A | A^T A (upper-packed as ug packs U), formed once here
+    std::vector<double> rec((size_t)kPriorRec * n);
+    int j = 0;
+    for (size_t i = 0; i < h->prior_idx.size(); ++i) {
+      if (h->ext_col[(size_t)h->prior_idx[i]] < 0) continue;
+      double* R = rec.data() + (size_t)kPriorRec * j++;
+      const double* A = h->prior_A.data() + 36 * i;
+      std::memcpy(R, h->prior_mean.data() + 6 * i, 6 * sizeof(double));
+      std::memcpy(R + 6, A, 36 * sizeof(double));
+      int q = 42;
+      for (int a = 0; a < 6; ++a)
+        for (int b = a; b < 6; ++b) {
+          double t = 0.0;
+          for (int r = 0; r < 6; ++r) t += A[6 * r + a] * A[6 * r + b];
+          R[q++] = t;
+        }
+    }
+    HIP_OK(hipMemcpyAsync(h->lz.d_prior_idx, idx.data(), sizeof(int2) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    HIP_OK(hipMemcpyAsync(h->lz.d_prior_rec, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice,
+                          h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));  // idx, rec go out of scope
+    h->prior_dirty = false;
+  }
+  // the arrival count starts every call that launches the prior kernels at zero
+  HIP_OK(hipMemsetAsync(h->lz.d_prior_cnt, 0, sizeof(unsigned) * 2, h->stream));
+  h->n_prior = n;
+  return 0;
+}
+extern "C" int dab_set_ext_priors(dab_handle* h, int32_t count, const int32_t* ext_index, const double* mean,
+                                  const double* sqrt_info) {
+  clear_error();
+  if (!h) return set_error(DAB_E_INVALID, "null handle");
+  if (!h->have_problem) return set_error(DAB_E_STATE, "no problem set");
+  if (count < 0) return set_error(DAB_E_INVALID, "negative prior count");
+  if (count > 0 && (!ext_index || !mean || !sqrt_info)) return set_error(DAB_E_INVALID, "null prior array");
+  std::vector<uint8_t> seen((size_t)std::max(1, h->E), 0);
+  for (int i = 0; i < count; ++i) {
+    const int e = ext_index[i];
+    if (e < 0 || e >= h->E) return set_error(DAB_E_INVALID, "prior on an extrinsic index out of range");
+    if (seen[(size_t)e]) return set_error(DAB_E_INVALID, "two priors on one extrinsic");
+    seen[(size_t)e] = 1;
+  }
+  for (size_t i = 0; i < (size_t)6 * count; ++i)
+    if (!std::isfinite(mean[i])) return set_error(DAB_E_INVALID, "prior mean is not finite");
+  for (size_t i = 0; i < (size_t)36 * count; ++i)
+    if (!std::isfinite(sqrt_info[i])) return set_error(DAB_E_INVALID, "prior sqrt_info is not finite");
+  h->prior_idx.assign(ext_index, ext_index + count);
+  h->prior_mean.assign(mean, mean + (size_t)6 * count);
+  h->prior_A.assign(sqrt_info, sqrt_info + (size_t)36 * count);
+  h->prior_dirty = true;
+  h->n_prior = 0;
+  return 0;
+}
+extern "C" int dab_get_ext_priors(dab_handle* h, int32_t* count, int32_t* num_effective, int32_t* ext_index,
+                                  double* mean, double* sqrt_info) {
+  clear_error();
+  if (!h) return set_error(DAB_E_INVALID, "null handle");
+  if (!h->have_problem) return set_error(DAB_E_STATE, "no problem set");
+  const size_t n = h->prior_idx.size();
+  if (count) *count = (int32_t)n;
+  if (num_effective) {
+    int c = 0;
+    for (int e : h->prior_idx) c += h->ext_col[(size_t)e] >= 0;
+    *num_effective = c;
+  }
+  if (ext_index) std::copy(h->prior_idx.begin(), h->prior_idx.end(), ext_index);
+  if (mean) std::copy(h->prior_mean.begin(), h->prior_mean.end(), mean);
+  if (sqrt_info) std::copy(h->prior_A.begin(), h->prior_A.end(), sqrt_info);
+  return 0;
+}
+extern "C" int dab_eval_ext_priors(dab_handle* h, double* residuals, double* cost) {
+  clear_error();
+  if (!h) return set_error(DAB_E_INVALID, "null handle");
+  if (!h->have_problem) return set_error(DAB_E_STATE, "no problem set");
+  HIP_OK(hipSetDevice(h->device));
+  CHECK_RC(prior_sync(h));
+  const int n = h->n_prior;
+  std::vector<double> res((size_t)6 * n + 1, 0.0);
+  if (n > 0) {
+    launch_prior_eval(h->stream, n, h->lz.d_prior_idx, h->lz.d_prior_rec, h->d_ext, h->lz.d_prior_res);
+    HIP_OK(hipMemcpyAsync(res.data(), h->lz.d_prior_res, sizeof(double) * res.size(), hipMemcpyDeviceToHost,
+                          h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));
+  }
+  if (residuals) {  // as set: an ignored prior's row is zero
+    int j = 0;
+    for (size_t i = 0; i < h->prior_idx.size(); ++i) {
+      const bool eff = h->ext_col[(size_t)h->prior_idx[i]] >= 0;
+      for (int k = 0; k < 6; ++k) residuals[6 * i + k] = eff ? res[(size_t)6 * j + k] : 0.0;
+      j += eff;
+    }
+  }
+  if (cost) *cost = res[(size_t)6 * n];
+  return guard_fail(h, "dab_eval_ext_priors");
+}
+
 extern "C" int dab_set_problem(dab_handle* h, const dab_problem* p) {
   const int rc = set_problem_impl(h, p);
   CHECK_RC(guard_fail(h, "dab_set_problem"));
@@ -1344,6 +1472,11 @@ static int set_problem_impl(dab_handle* h, const dab_problem* p) {
   h->pt_const_dirty = true;
   h->d_ptc = nullptr;
   h->n_pt_const = 0;
+  h->prior_idx.clear();  // no priors (num_ext may have changed)
+  h->prior_mean.clear();
+  h->prior_A.clear();
+  h->prior_dirty = true;
+  h->n_prior = 0;
   PhaseTimer phase{"set_problem %-22s %8.1f ms\n"};  // the host preprocessing's phases
   const int N = p->num_obs;
   h->N = N;

@@ -240,6 +240,10 @@ int dab::eval_jacobian_and_blocks(dab_handle* h, bool with_norms, bool tables_cu
   hipStream_t s = h->stream;
   if (!tables_current) launch_cam_tables(s, h->E, h->d_ext, h->d_camtab);
   CHECK_RC(eval_pass(h, true));
+  // extrinsic priors: A^T A | A^T r into the camera rows, after the pass's sum over the ranks (the
+  // overlapped one too) and before the norms, the Jacobi scale and every step kernel read them
+  launch_prior_blocks(s, h->n_prior, h->lz.d_prior_idx, h->lz.d_prior_rec, h->d_ext, h->ug(), h->lz.d_prior_part,
+                      h->lz.d_prior_cnt, h->d_scal + S_PRIOR);
   if (with_norms) {
     launch_grad_points_m(s, h->NP, h->d_points, h->d_g, h->d_gpart, h->red_grid, h->d_ptc);
     launch_final_sum(s, h->red_grid, 3, h->d_gpart, h->d_scal + S_GMAX_P, 1u);
@@ -532,6 +536,7 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
   HIP_OK(hipSetDevice(h->device));
   // constant points: this rank's set, and whether any rank has a free point left
   CHECK_RC(pt_const_sync(h));
+  CHECK_RC(prior_sync(h));  // the effective extrinsic priors (none: no prior kernel is launched)
   int pstate = 2;
   CHECK_RC(points_state(h, &pstate));
   const bool no_free_points = pstate == 1;
@@ -590,7 +595,7 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
   sum->iterations_written = 0;
   sum->num_successful_steps = sum->num_unsuccessful_steps = 0;
   sum->num_iterations = 0;
-  sum->num_residuals = 2 * h->N;
+  sum->num_residuals = 2 * h->N + 6 * h->n_prior;
   sum->num_parameters = 3 * (NP - h->n_pt_const) + 6 * NC + cs.nz_scal;
   sum->num_free_points = NP - h->n_pt_const;
   sum->num_free_ext = NC;
@@ -633,8 +638,10 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
   if (timing) std::fprintf(stderr, "solve iteration 0: %.2f ms\n", 1e3 * (now_s() - t0));
   launch_jacobi_scale(h, nfi, opt.jacobi_scaling);
   sum->jacobian_evaluation_time_in_seconds += now_s() - t0;
-  double x_cost = 0.5 * h->h_scal[S_COST];
-  bool eval_ok = h->h_scal[S_COST_BAD] == 0.0;
+  // x_obs: the observations' part, which bounds the tile assembly's fixed-point rhs
+  double x_obs = 0.5 * h->h_scal[S_COST];
+  double x_cost = h->n_prior > 0 ? x_obs + prior_cost(h) : x_obs;
+  bool eval_ok = h->h_scal[S_COST_BAD] == 0.0 && std::isfinite(prior_cost(h));
   double gmax = std::max(h->h_scal[S_GMAX_P], h->h_scal[S_CAM0 + 2]);
   double x_norm = std::sqrt(h->h_scal[S_XNORM_P] + h->h_scal[S_CAM0 + 4]);
   if (nfi > 0) {
@@ -735,7 +742,7 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
       it.linear_solver_iterations = cg_iters;
       pcg_fail = cg_status == kPcgFailure;
     } else if (NC > 0) {
-      CHECK_RC(cam_system_assemble(h, cs, sc, x_cost, true));
+      CHECK_RC(cam_system_assemble(h, cs, sc, x_obs, true));
       CHECK_RC(intr_border_rows(h, nfi, sc, cs.S, cs.ld));
       if (chol_factor_solve(h->chol, s, n2, cs.S, cs.ld, yc_, h->d_flags + 1) != 0)
         return set_error(DAB_E_DEVICE, "dense Cholesky launch failed");
@@ -767,6 +774,9 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
     }
     launch_final_sum(s, h->red_grid, 3, h->d_gpart, h->d_scal + S_MODEL);
     CHECK_RC(h->allreduce(h->d_scal + S_MODEL, 5, ncclSum));
+    // the priors' part of the model cost change and of the candidate's cost, once, after the sum
+    launch_prior_candidate(s, h->n_prior, h->lz.d_prior_idx, h->lz.d_prior_rec, h->d_ext, h->d_ext_c, h->d_dc,
+                           h->lz.d_prior_part, h->lz.d_prior_cnt, h->d_scal + S_MODEL);
     CHECK_RC(h->allreduce_max_i32(h->d_flags, 4));
     CHECK_RC(read_znorm());
     CHECK_RC(read_scalars(h));
@@ -837,12 +847,13 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
       CHECK_RC(read_znorm());
       CHECK_RC(read_scalars(h));
       sum->jacobian_evaluation_time_in_seconds += now_s() - tj;
-      if (h->h_scal[S_COST_BAD] != 0.0) {
+      if (h->h_scal[S_COST_BAD] != 0.0 || !std::isfinite(prior_cost(h))) {
         term = DAB_FAILURE;
         std::snprintf(sum->message, sizeof(sum->message), "Residual and Jacobian evaluation failed.");
         break;
       }
-      x_cost = 0.5 * h->h_scal[S_COST];
+      x_obs = 0.5 * h->h_scal[S_COST];
+      x_cost = h->n_prior > 0 ? x_obs + prior_cost(h) : x_obs;
       gmax = std::max(h->h_scal[S_GMAX_P], h->h_scal[S_CAM0 + 2]);
       if (nfi > 0) gmax = std::max(gmax, hz[8 + 2]);
       it.step_is_successful = 1;

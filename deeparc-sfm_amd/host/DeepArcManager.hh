@@ -71,6 +71,22 @@ class DeepArcManager {
   // groups and applied after every dab_set_problem.
   void setPointsConstant(bool all) { points_const_ = all; }
   bool pointsConstant() const { return points_const_; }
+  // Gaussian priors on extrinsics for every later solve() of this manager (dab_set_ext_priors in
+  // dab.h; Ceres: problem.AddResidualBlock(new NormalPrior(A, mu), NULL, ext)): index in
+  // extrinsics(), mean [n][6] = (rotation, translation) as the Extrinsic stores them, sqrt_info
+  // [n][6][6] row-major = A of the residual A (x - mean). Empty vectors clear them. Kept across
+  // the pipeline's re-set-ups beside the loss, the groups and the point flag and applied after
+  // every dab_set_problem; checked when the solve applies them to the handle. A prior on a
+  // constant extrinsic (the gauge rule's, or all of them under freeze_camera) is ignored.
+  void setExtrinsicPriors(const std::vector<int>& index, const std::vector<double>& mean,
+                          const std::vector<double>& sqrt_info) {
+    prior_index_ = index;
+    prior_mean_ = mean;
+    prior_sqrt_info_ = sqrt_info;
+  }
+  const std::vector<int>& extrinsicPriorIndex() const { return prior_index_; }
+  const std::vector<double>& extrinsicPriorMean() const { return prior_mean_; }
+  const std::vector<double>& extrinsicPriorSqrtInfo() const { return prior_sqrt_info_; }
 
   // Covariance of the current scene at its current parameters (dab_covariance in dab.h: Sigma =
   // (J^T J)^-1 under this manager's loss, no sigma^2 factor; ceres::Covariance). The reference's
@@ -111,6 +127,8 @@ class DeepArcManager {
   double loss_scale_ = 1.0;
   int intr_free_ = 0;  // all constant (sfm.cc:60-62)
   bool points_const_ = false;  // all free (sfm.cc:59 commented out)
+  std::vector<int> prior_index_;  // extrinsic priors (none)
+  std::vector<double> prior_mean_, prior_sqrt_info_;
   int arc_size_ = 0, ring_size_ = 0;
   bool share_extrinsic_ = false;
   std::map<int, std::map<int, Camera*> > hemisphere_;

@@ -158,6 +158,23 @@ int dam_set_points_constant(dam_manager* m, int32_t all) {
   });
 }
 
+int dam_set_ext_priors(dam_manager* m, int32_t count, const int32_t* ext_index, const double* mean,
+                       const double* sqrt_info) {
+  return guarded([&] {
+    if (!m) throw "null manager";
+    if (count < 0) throw "negative prior count";
+    if (count > 0 && (!ext_index || !mean || !sqrt_info)) throw "null prior array";
+    const size_t n = (size_t)count;
+    const size_t next = m->m.extrinsics()->size();
+    for (size_t i = 0; i < n; ++i)
+      if (ext_index[i] < 0 || (size_t)ext_index[i] >= next) throw "prior on an extrinsic index out of range";
+    if (n == 0) m->m.setExtrinsicPriors({}, {}, {});
+    else
+      m->m.setExtrinsicPriors(std::vector<int>(ext_index, ext_index + n), std::vector<double>(mean, mean + 6 * n),
+                              std::vector<double>(sqrt_info, sqrt_info + 36 * n));
+  });
+}
+
 int dam_covariance(dam_manager* m, const int32_t* extra_const, int32_t n_extra, int32_t freeze_camera,
                    double* point_cov, double* ext_cov, double* ext_full, int32_t* ext_label,
                    dab_covariance_info* info) {

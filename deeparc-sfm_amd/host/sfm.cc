@@ -42,6 +42,13 @@ int solveWith(DeepArcManager& m, const dab_options& options, bool freeze_camera,
     rc = dab_set_points_constant(dh.h, nullptr);
   }
   if (rc) return rc;
+  // the extrinsic priors, or none: after every (re-)set-up, which resets them on the handle
+  {
+    const std::vector<int32_t> idx(m.extrinsicPriorIndex().begin(), m.extrinsicPriorIndex().end());
+    rc = dab_set_ext_priors(dh.h, (int32_t)idx.size(), idx.data(), m.extrinsicPriorMean().data(),
+                            m.extrinsicPriorSqrtInfo().data());
+  }
+  if (rc) return rc;
   const double t0 = dab_now_seconds();
   rc = dab_solve(dh.h, &options, s);
   // (not with free intrinsics: they need the exact step, and PCG's refusal would hide the reason)

@@ -47,6 +47,7 @@ SIGNATURES = {
     "dam_set_loss": (C.c_int, [C.c_void_p, C.c_int32, C.c_double]),
     "dam_set_intrinsics_free": (C.c_int, [C.c_void_p, C.c_int32]),
     "dam_set_points_constant": (C.c_int, [C.c_void_p, C.c_int32]),
+    "dam_set_ext_priors": (C.c_int, [C.c_void_p, C.c_int32, _ip, _dp, _dp]),
     "dam_covariance": (C.c_int, [C.c_void_p, _ip, C.c_int32, C.c_int32, _dp, _dp, _dp, _ip,
                                  C.POINTER(_abi.DabCovarianceInfo)]),
     "dam_covariance_intrinsics": (C.c_int, [C.c_void_p, _ip, C.c_int32, _dp, _dp, _dp, _dp, _ip, _ip,
@@ -161,6 +162,21 @@ class DeepArcManager:
         """Every later solve() of this manager holds all points constant (dam_set_points_constant):
         the reference's commented-out sfm.cc:59; False frees them again."""
         _check(self.lib.dam_set_points_constant(self.h, int(bool(all_points))))
+
+    def set_ext_priors(self, index, mean=None, sqrt_info=None):
+        """Gaussian priors on extrinsics for every later solve() of this manager
+        (dam_set_ext_priors; core.Solver.set_ext_priors' arguments, index in extrinsics()); None or
+        an empty index clears them."""
+        if index is None or np.size(index) == 0:
+            _check(self.lib.dam_set_ext_priors(self.h, 0, None, None, None))
+            return
+        idx = np.ascontiguousarray(index, np.int32).reshape(-1)
+        n = idx.shape[0]
+        mu = np.ascontiguousarray(mean, np.float64)
+        a = np.ascontiguousarray(sqrt_info, np.float64)
+        if mu.shape != (n, 6) or a.shape != (n, 6, 6):
+            raise ValueError(f"mean: ({n}, 6) and sqrt_info: ({n}, 6, 6) values")
+        _check(self.lib.dam_set_ext_priors(self.h, n, _p(idx, C.c_int32), _p(mu, C.c_double), _p(a, C.c_double)))
 
     def covariance(self, extra_const=(), freeze_camera=False, full=False):
         """DeepArcManager::covariance (dam_covariance): the covariance of the current scene at its

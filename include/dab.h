@@ -376,6 +376,58 @@ int dab_get_intrinsic_blocks(dab_handle* h, int32_t* num_free_intr, double* zg /
 int dab_set_points_constant(dab_handle* h, const uint8_t* mask /* [num_points], caller order; NULL = all free */);
 int dab_get_points_constant(dab_handle* h, uint8_t* mask /* nullable */, int32_t* num_constant /* nullable */);
 
+/* ---- Gaussian priors on extrinsics ------------------------------------------------------
+ * "This pose is known to within sigma", without holding it constant: what in Ceres is
+ *   problem.AddResidualBlock(new ceres::NormalPrior(A, mu), NULL, ext)
+ * on an extrinsic's block. A prior adds the residual block r = A (x_e - mu) to the problem,
+ * x_e = ext[e] = (w, t) as the library stores it (the angle-axis vector as it stands, no rotation
+ * manifold), A = sqrt_info 6x6 row-major. Rows of A may be zero: a position-only prior is
+ * A = [0 0; 0 I / sigma]. The prior adds 0.5 |r|^2 to every cost dab_solve and the covariance
+ * calls report and is never under the handle's robust loss (a NULL loss of its own). Uses: a rig
+ * whose arcs and rings have design values (between "constant" and "free"), and the soft remedy
+ * for the scale gauge dab_covariance needs: a position prior on one or a few cameras gives a
+ * covariance that carries that uncertainty instead of claiming it is zero.
+ *
+ * The priors are state of the handle, like the loss and the masks: set after dab_set_problem,
+ * which resets them to none (num_ext may change); they survive dab_update_parameters,
+ * dab_set_loss, dab_set_intrinsics_free and dab_set_points_constant and take effect at the next
+ * dab_solve, dab_covariance or dab_covariance_intrinsics. count = 0 (arrays may be NULL) clears
+ * them. At most one prior per extrinsic. In a multi-rank handle every rank sets the same priors
+ * (extrinsics are replicated; the prior's sums are added once, after the sums over the ranks,
+ * identically on every rank).
+ *
+ * Effective set. A prior is effective when its extrinsic is in the free set the solve uses:
+ * referenced on some rank, not ext_const, freeze_camera not set. Any other prior is ignored
+ * entirely: no cost, no residual rows, zeros from dab_eval_ext_priors. This is a deliberate
+ * simplification: Ceres would carry the constant cost of such a block. *num_effective counts
+ * the effective priors; dab_summary.num_residuals and dab_covariance_info.num_residuals grow by 6
+ * per effective prior, num_parameters is unchanged. With no effective prior (never set, count 0,
+ * only constant or unreferenced extrinsics named, freeze_camera) every call gives bitwise what it
+ * gives on a handle that never set one, and no prior kernel is launched.
+ *
+ * Where it enters: A^T A and A^T r are added to the camera's U | g_c row after each evaluation
+ * pass and its all-reduce, so every linear solver, assembly, pcg_fp32, loss, free-intrinsics and
+ * constant-points combination that works without priors works with them (there are no new
+ * DAB_E_UNSUPPORTED cases); the model cost change and the candidate cost get the prior's terms
+ * after the candidate pass. Every prior sum has a fixed order: two solves agree bitwise.
+ *
+ * dab_get_ext_priors returns what was set (arrays nullable, sized by a first call for *count).
+ * dab_eval_ext_priors evaluates at the parameters now on the handle: residuals [count][6] in the
+ * order set, cost = 0.5 sum |r|^2 over the effective priors.
+ *
+ * dab_eval_residuals, dab_eval_jacobians, dab_filter, dab_bench_eval_pass, dab_bench_get_blocks,
+ * dab_get_intrinsic_blocks and dab_jacobian_bytes ignore priors (raw observation quantities;
+ * dab_bench_get_blocks reads the camera rows where the last evaluation left them: raw after
+ * dab_bench_eval_pass, with A^T A | A^T r added after a dab_solve or covariance call with priors).
+ * Errors, all leaving the state unchanged: DAB_E_INVALID for a null handle (checked before any
+ * device use), count < 0, a null array with count > 0, an index outside [0, num_ext), a duplicate
+ * index, or a non-finite entry of mean or sqrt_info; DAB_E_STATE before dab_set_problem. */
+int dab_set_ext_priors(dab_handle* h, int32_t count, const int32_t* ext_index /* [count] */,
+                       const double* mean /* [count][6] */, const double* sqrt_info /* [count][6][6] row-major */);
+int dab_get_ext_priors(dab_handle* h, int32_t* count, int32_t* num_effective, int32_t* ext_index, double* mean,
+                       double* sqrt_info);
+int dab_eval_ext_priors(dab_handle* h, double* residuals /* [count][6], as set; nullable */, double* cost /* nullable */);
+
 /* ---- evaluation (parity / filterPoint3d) ---------------------------------------------
  * residuals: [num_obs][2] in the caller's observation order.
  * jacobians: [num_obs][2][15] row-major, columns = [X(3) | w0(3) t0(3) | w1(3) t1(3)]
@@ -441,7 +493,8 @@ int dab_filter(dab_handle* h, double error_boundary, const double center[3], dou
  * still sit in U and S would be overconfident. Remedies: drop such points from the problem
  * (Problem.subset in the Python layer), and fix the scale gauge with one constant point
  * (dab_set_points_constant: a ground-control point) or with one more constant extrinsic
- * (ext_const) beside the reference's arc 0 / camera 0.
+ * (ext_const) beside the reference's arc 0 / camera 0; or, softly, with a position prior on one
+ * or a few cameras (dab_set_ext_priors), whose uncertainty the covariance then carries.
  *
  * Multi-rank handles: every rank calls it. S is all-reduced as in the exact step, every rank
  * inverts its own copy (identical camera arrays) and gets the covariances of its own shard's

@@ -65,6 +65,16 @@ int dam_set_intrinsics_free(dam_manager* m, int32_t groups);
  * sfm.cc:59, all or nothing as that line is). 0, the default, frees them again. Re-applied after
  * every re-set of the resident problem, like the loss and the intrinsic groups. */
 int dam_set_points_constant(dam_manager* m, int32_t all);
+/* Gaussian priors on extrinsics for every later solve of this manager (dab_set_ext_priors in
+ * dab.h; Ceres: problem.AddResidualBlock(new NormalPrior(A, mu), NULL, ext)): ext_index [count]
+ * in the order of dam_get_cameras' extrinsics, mean [count][6] = (rotation, translation),
+ * sqrt_info [count][6][6] row-major = A of the residual A (x - mean). count = 0 clears them. An
+ * index outside the manager's extrinsics, a negative count or a null array with count > 0 return an
+ * error and leave the setting as it was; duplicates and non-finite entries are refused by the
+ * solve that applies them. Re-applied after every re-set of the resident problem, like the loss,
+ * the groups and the point flag; a prior on a constant extrinsic is ignored. */
+int dam_set_ext_priors(dam_manager* m, int32_t count, const int32_t* ext_index, const double* mean,
+                       const double* sqrt_info);
 /* DeepArcManager::covariance: dab_covariance (dab.h) of the manager's current scene at its
  * current parameters, under the manager's loss. extra_const[n_extra]: extrinsic indices held
  * constant beside the gauge rule's; the reference's rule leaves the rig's global scale free

@@ -15,6 +15,10 @@ step only: pair it with --solvers explicit).
 (dab_set_points_constant) on every rank's shard and on the single handle; the constant points must
 come back bitwise untouched, and with `all` every rank must report the direct camera step
 (DAB_SCHUR_DIRECT) for the explicit and the AUTO solver (pair it with --solvers explicit,auto).
+--ext-priors pose sets a full Gaussian prior on every non-constant extrinsic (dab_set_ext_priors),
+the same on every rank's handle and on the single handle: a prior added once per rank instead of
+once shows as a cost difference far above --tol (the priors' share of the initial cost is printed
+and must be above 100 --tol). Off by default.
 --expect-auto-refused checks instead that LINEAR_SOLVER_AUTO, where it picks PCG (several ranks, a
 camera system that is not a small one), refuses a non-empty free set on every rank.
 --covariance checks dab_covariance instead: every rank calls it on its shard after the solve, and
@@ -68,6 +72,8 @@ def main():
     ap.add_argument("--const-points", default="", choices=("", "third", "all"),
                     help="constant points on every handle: every third point by global id, or all of them (then "
                     "every rank must take the direct camera step, S = U + D^2, also under AUTO)")
+    ap.add_argument("--ext-priors", default="", choices=("", "pose"),
+                    help="Gaussian priors on every non-constant extrinsic, the same on every handle")
     ap.add_argument("--expect-auto-refused", action="store_true",
                     help="with --free-intrinsics: a rig whose tables do not fit the small-camera paths (135 "
                     "extrinsics), so AUTO picks PCG on several ranks; every rank's dab_solve must return "
@@ -260,6 +266,16 @@ def main():
             cmask = np.ones(glob.points.shape[0], bool)
             if a.const_points == "third":
                 cmask = np.arange(glob.points.shape[0]) % 3 == 0
+        priors = None
+        if a.ext_priors:
+            # A = Q D (I + 0.2 G), D = diag(1/0.02 x3, 1/0.05 x3); mean = start + sigma o normal
+            rng = np.random.default_rng(11)
+            sig = np.array([0.02] * 3 + [0.05] * 3)
+            pidx = np.flatnonzero(glob.ext_const == 0).astype(np.int32)
+            pa = np.stack([np.linalg.qr(rng.standard_normal((6, 6)))[0] @ np.diag(1.0 / sig)
+                           @ (np.eye(6) + 0.2 * rng.standard_normal((6, 6))) for _ in pidx])
+            priors = (pidx, glob.ext[pidx] + sig * rng.standard_normal((len(pidx), 6)), pa)
+        prior_share = 0.0
         live = []
         if a.live_together:  # every handle of this problem created (and its arena slot taken) up front
             for _ in range(3):
@@ -280,6 +296,10 @@ def main():
                     s1.set_intrinsics_free(a.free_intrinsics)
                 if cmask is not None:
                     s1.set_points_constant(cmask)
+                if priors is not None:
+                    s1.set_ext_priors(*priors)
+                    assert s1.get_ext_priors()[3] == len(priors[0])
+                    prior_share = s1.eval_ext_priors()[1]
                 ropts = opts
                 if lst == pkg.DAB_LINEAR_SOLVER_AUTO:
                     # what AUTO must pick on several ranks: the exact step for small camera
@@ -288,6 +308,7 @@ def main():
                             if glob.ext.shape[0] <= 160 or a.const_points == "all" else pkg.DAB_LINEAR_SOLVER_IMPLICIT_SCHUR_PCG)
                     ropts = pkg.options(max_num_iterations=a.iters, linear_solver_type=want)
                 ref = (s1.solve(ropts), g1.points.copy(), g1.ext.copy(), g1.intr.copy())
+                prior_share /= ref[0]["initial_cost"]
                 s1.close()
             dist.barrier()
             mine = glob.copy().shard(rank, world)
@@ -300,6 +321,8 @@ def main():
                 s.set_intrinsics_free(a.free_intrinsics)  # the same mask on every rank (include/dab.h)
             if cmask is not None:
                 s.set_points_constant(cmask)  # the shard's points are the ones this rank references
+            if priors is not None:
+                s.set_ext_priors(*priors)  # the same priors on every rank (include/dab.h)
             sched = s.eval_fused()
             p2p = s.comm_p2p()
             summ = s.solve(opts)
@@ -339,6 +362,7 @@ def main():
                     intr_ranks_equal=bool(torch.equal(kk, kk_min)),
                     intr_moved=float(np.abs(rk - glob.intr).max()) if rk.size else 0.0,
                     num_parameters=(summ["num_parameters"], rs["num_parameters"]),
+                    num_residuals=(summ["num_residuals"], rs["num_residuals"], 2 * glob.num_obs), prior_share=prior_share,
                     eval_schedule=sched, p2p=p2p,
                     assembly=(int(asm[0]), -int(asm[1]), rs["schur_assembly"]), const_held=bool(held.item()),
                     solver_used=(summ["linear_solver_type_used"], rs["linear_solver_type_used"]))
@@ -359,6 +383,7 @@ def main():
                or (a.expect_p2p and v["p2p"] != 1)
                or (a.expect_no_p2p and v["p2p"] != 0)
                or not v["const_held"]
+               or (a.ext_priors and not (v["prior_share"] > 100 * a.tol and v["num_residuals"][1] > v["num_residuals"][2]))
                or (a.const_points == "all" and v["solver_used"][0] == pkg.DAB_LINEAR_SOLVER_EXPLICIT_SCHUR
                    and v["assembly"] != (pkg.DAB_SCHUR_DIRECT,) * 3)
                or v["solver_used"][0] != v["solver_used"][1]]
