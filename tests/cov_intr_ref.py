@@ -1,13 +1,14 @@
-"""TEST INFRASTRUCTURE ONLY: the numpy reference of dab_covariance_intrinsics (a plain module).
+"""TEST INFRASTRUCTURE ONLY: the arrays of dab_covariance_intrinsics from a dense Sigma (a plain
+module).
 
 Sigma = (J^T J)^-1 over the referenced points, the free extrinsics and the active intrinsic
-scalars (intr_ref._Layout: the scalars dab_solve counts), J the oracle's rows beside intr_ref.jz's
-six intrinsic columns, both scaled by sqrt(rho') under a loss (robust_ref.correct). Sigma is
+scalars (lm_ref.Layout: the scalars dab_solve counts), J from lm_ref.jacobian. Sigma is
 cov_ref.sigma_inv of that Jacobian, pinned against cov_ref.sigma_pinv by
-tests/test_cov_intr_ref.py, and split into the arrays of the call: inactive slots (the model
-lacks them or the mask leaves them out) get zero rows and columns. kappa is that of the
-Jacobi-scaled H over all columns; the rank test is cov_ref.rank_test with the z columns beside
-the cameras'. Also the cases the CPU and GPU tests share.
+tests/test_cov_intr_ref.py, and split by blocks() into the arrays of the call: inactive slots (the
+model lacks them or the mask leaves them out) get zero rows and columns; without a free scalar
+cam_full is dab_covariance's ext_full. kappa is that of the Jacobi-scaled H over all columns; the
+rank test is cov_ref.rank_test with the z columns beside the cameras'. Also the cases the CPU and
+GPU tests share.
 """
 from types import SimpleNamespace
 
@@ -16,15 +17,6 @@ import numpy as np
 import cov_ref as cr
 import intr_ref as ir
 import robust_ref as rr
-
-
-def jacobian(pkg, orc, prob, groups, loss=(rr.TRIVIAL, 1.0)):
-    """(layout, dense [2 N][n] Jacobian of the loss-corrected rows, 0.5 sum rho)."""
-    r, J = orc.eval_jacobians(pkg, prob)
-    J21 = np.concatenate([J, ir.jz(prob)], axis=2)
-    _, Jt, ps = rr.correct(loss[0], loss[1], r, J21)
-    L = ir._Layout(prob, groups)
-    return L, L.dense(Jt[:, :, :15], Jt[:, :, 15:]), 0.5 * ps.sum()
 
 
 def free_intrinsics(L):
@@ -62,15 +54,6 @@ def blocks(Sigma, L, prob):
 def rank_test(A, L, thr=cr.MIN_PIVOT_RATIO):
     """cov_ref.rank_test with the active intrinsic columns beside the cameras' in the reduced system."""
     return cr.rank_test(A, SimpleNamespace(np=L.np, nc=L.nc + int(L.nz > 0)), thr)
-
-
-def reference(pkg, orc, prob, groups, loss=(rr.TRIVIAL, 1.0)):
-    """Everything a GPU test compares against, computed once per case."""
-    L, A, cost = jacobian(pkg, orc, prob, groups, loss)
-    out = blocks(cr.sigma_inv(A), L, prob)
-    out.update(kappa=cr.kappa(A), cost=cost, num_parameters=L.n, num_residuals=A.shape[0], num_free_scalars=L.nz,
-               layout=L)
-    return out
 
 
 def bound(ref):

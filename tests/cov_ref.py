@@ -1,8 +1,9 @@
-"""TEST INFRASTRUCTURE ONLY: the numpy reference of dab_covariance (a plain module).
+"""TEST INFRASTRUCTURE ONLY: the covariance mathematics of the numpy reference of dab_covariance
+(a plain module).
 
-Sigma = (J^T J)^-1 over the free parameters (robust_ref._Layout: referenced points, then
-referenced non-constant extrinsics), J the oracle's Jacobian rows scaled by sqrt(rho') under a
-loss (robust_ref.correct). Two routes, pinned against each other by tests/test_cov_ref.py:
+Sigma = (J^T J)^-1 over the free parameters (lm_ref.Layout), J the dense Jacobian of
+lm_ref.jacobian; lm_ref.covariance splits it into the call's arrays. Two routes, pinned against
+each other by tests/test_cov_ref.py:
   * sigma_inv: inv of the Jacobi-scaled H = (J s)^T (J s), unscaled (the library's variables);
   * sigma_pinv: pinv(J) pinv(J)^T (the SVD route, what Ceres' DENSE_SVD computes).
 Also kappa of the scaled H (the accuracy bound of the GPU tests is 64 kappa 2^-53 max|Sigma|),
@@ -15,14 +16,6 @@ import robust_ref as rr
 
 MIN_PIVOT_RATIO = 1e-10
 EPS = 2.0 ** -53
-
-
-def jacobian(pkg, orc, prob, loss=(rr.TRIVIAL, 1.0)):
-    """(layout, dense [2 N][n] Jacobian of the loss-corrected rows, 0.5 sum rho)."""
-    r, J = orc.eval_jacobians(pkg, prob)
-    _, Jt, ps = rr.correct(loss[0], loss[1], r, J)
-    L = rr._Layout(prob)
-    return L, L.dense(Jt), 0.5 * ps.sum()
 
 
 def jacobi_scale(A, on=True):
@@ -92,28 +85,6 @@ def rank_test(A, L, thr=MIN_PIVOT_RATIO):
     piv = _chol_pivots(0.5 * (S + S.T))
     cr = 0.0 if (len(piv) < S.shape[0] or not piv[-1] > 0.0) else float(piv.min() / piv.max())
     out.update(camera_ratio=cr, deficient=not cr > thr)
-    return out
-
-
-def blocks(Sigma, L, prob):
-    """dab_covariance's arrays from the dense Sigma: point_cov (num_points, 3, 3) with NaN rows
-    for unreferenced points, ext_cov (nc, 6, 6), ext_full (6 nc, 6 nc), ext_index."""
-    npts = prob.points.shape[0]
-    pc = np.full((npts, 3, 3), np.nan)
-    for i, p in enumerate(L.pt_of):
-        pc[p] = Sigma[3 * i:3 * i + 3, 3 * i:3 * i + 3]
-    n3 = 3 * L.np
-    full = Sigma[n3:, n3:].copy()
-    ec = np.stack([full[6 * c:6 * c + 6, 6 * c:6 * c + 6] for c in range(L.nc)]) if L.nc else np.zeros((0, 6, 6))
-    return dict(point_cov=pc, ext_cov=ec, ext_full=full, ext_index=L.ext_of.astype(np.int32))
-
-
-def reference(pkg, orc, prob, loss=(rr.TRIVIAL, 1.0)):
-    """Everything a GPU test compares against, computed once per case: the blocks of sigma_inv,
-    kappa, cost and the sizes."""
-    L, A, cost = jacobian(pkg, orc, prob, loss)
-    out = blocks(sigma_inv(A), L, prob)
-    out.update(kappa=kappa(A), cost=cost, num_parameters=L.n, num_residuals=A.shape[0], layout=L)
     return out
 
 

@@ -1,17 +1,17 @@
-"""TEST INFRASTRUCTURE ONLY: the reference for the free-intrinsics tests (a plain module).
+"""TEST INFRASTRUCTURE ONLY: the intrinsic columns and the shapes of the free-intrinsics tests (a
+plain module).
 
 oracle/ restates the reference's solve with constant intrinsics (sfm.cc:60-62) and cannot grow
-intrinsic columns, so the self-calibrating LM is pinned here:
+intrinsic columns, so the self-calibrating LM is pinned by lm_ref.lm over what is here:
   * jz(): the six analytic columns d r / d (cx, cy, f0, f1, k0, k1) of every observation in
     numpy, for every (nf, nk), single and composed observations (checked against central
     differences of the oracle's residual in tests/test_intr_ref.py);
-  * lm(): robust_ref.lm with the parameter layout extended by the active intrinsic scalars
-    after the extrinsics: the same float64 loop and dense Cholesky, statement by statement.
-    Its own summation order shows on one shape: with per-camera intrinsics and all groups free
-    the problem is weakly constrained, a one-ulp difference in an early step grows about 2.5
-    times per iteration, and over 15 iterations two listings of the same problem differ by
-    0.9e-10 .. 1.7e-10 of the cost (five orders tried; 4e-13 or less on the other shapes). That
-    is the float64 uncertainty of any implementation on that shape, the code under test included.
+  * active_mask(): the scalars that lm_ref.Layout puts after the extrinsics.
+lm_ref.lm's own summation order shows on one shape: with per-camera intrinsics and all groups
+free the problem is weakly constrained, a one-ulp difference in an early step grows about 2.5
+times per iteration, and over 15 iterations two listings of the same problem differ by
+0.9e-10 .. 1.7e-10 of the cost (five orders tried; 4e-13 or less on the other shapes). That
+is the float64 uncertainty of any implementation on that shape, the code under test included.
 Also the shapes the CPU and GPU tests share.
 """
 import numpy as np
@@ -19,7 +19,6 @@ import numpy as np
 import robust_ref as rr
 
 CENTER, FOCAL, DISTORTION = 1, 2, 4
-DBL_MAX = rr.DBL_MAX
 
 
 def _rot(w):
@@ -96,181 +95,6 @@ def jz(prob):
     J[:, 0, 5] = fx * r2 * r2 * xp
     J[:, 1, 5] = fy * r2 * r2 * yp
     return J * struct_mask(prob)[prob.obs_intr][:, None, :]
-
-
-class _Layout(rr._Layout):
-    """robust_ref's layout, then the active scalars of the free intrinsics in (index, slot) order."""
-
-    def __init__(self, prob, groups):
-        super().__init__(prob)
-        self.n_pc = self.n
-        self.act = active_mask(prob, groups)
-        self.zi, self.zk = np.nonzero(self.act)
-        self.nz = len(self.zi)
-        zcol = -np.ones(self.act.shape, np.int64)
-        zcol[self.zi, self.zk] = self.n_pc + np.arange(self.nz)
-        self.zcol = zcol[prob.obs_intr]  # [N][6]
-        self.n = self.n_pc + self.nz
-
-    def pack(self, prob):
-        return np.concatenate([super().pack(prob), prob.intr[self.zi, self.zk]])
-
-    def unpack(self, x, prob):
-        prob.points[self.pt_of] = x[:3 * self.np].reshape(-1, 3)
-        prob.ext[self.ext_of] = x[3 * self.np:self.n_pc].reshape(-1, 6)
-        prob.intr[self.zi, self.zk] = x[self.n_pc:]
-
-    def dense(self, J, Jz):
-        N = J.shape[0]
-        A = np.zeros((2 * N, self.n))
-        o, k = np.nonzero(self.col >= 0)
-        c = self.col[o, k]
-        A[2 * o, c] = J[o, 0, k]
-        A[2 * o + 1, c] = J[o, 1, k]
-        o, k = np.nonzero(self.zcol >= 0)
-        c = self.zcol[o, k]
-        A[2 * o, c] = Jz[o, 0, k]
-        A[2 * o + 1, c] = Jz[o, 1, k]
-        return A
-
-
-def lm(pkg, orc, prob, opts, groups=0, loss=(rr.TRIVIAL, 1.0)):
-    """robust_ref.lm with the active intrinsic scalars of `groups` as unknowns, in place on
-    prob.points / prob.ext / prob.intr. Returns a dict shaped like core.summary_to_dict."""
-    kind, a = loss
-    L = _Layout(prob, groups)
-    n = L.n
-    work = prob.copy()  # evaluation point
-    cand = prob.copy()
-    x = L.pack(prob)
-    x_norm = np.sqrt((x * x).sum())
-    its = []
-    state = {}
-
-    def evaluate(p):
-        r, J = orc.eval_jacobians(pkg, p)
-        ok = bool(np.isfinite(r).all())
-        J21 = np.concatenate([J, jz(p)], axis=2)
-        rt, Jt, ps = rr.correct(kind, a, r, J21)
-        A = L.dense(Jt[:, :, :15], Jt[:, :, 15:])
-        rv = rt.ravel()
-        g = A.T @ rv
-        state.update(A=A, r=rv, g=g)
-        d = x - (x + (-g))
-        return 0.5 * ps.sum(), (np.abs(d).max() if n else 0.0), ok
-
-    iteration = 0
-    radius, decrease_factor = opts.initial_trust_region_radius, 2.0
-    minimum_cost = DBL_MAX
-    xbest = x.copy()
-    num_invalid = 0
-    out = dict(num_successful_steps=0, num_unsuccessful_steps=0, num_parameters=n,
-               num_free_points=L.np, num_free_ext=L.nc, num_residuals=2 * prob.num_obs)
-    x_cost, gmax, ok = evaluate(work)
-    scale = np.ones(n)
-    if opts.jacobi_scaling:
-        scale = 1.0 / (1.0 + np.sqrt((state["A"] ** 2).sum(axis=0)))
-    out["initial_cost"] = x_cost
-    final_cost_min = x_cost
-    term, message = "FAILURE", ""
-    if not ok:
-        message = "Residual and Jacobian evaluation failed."
-    step_is_successful, step_is_valid = True, True
-    cost_change = step_norm = rel_decrease = 0.0
-    iter_cost = x_cost
-    while ok:
-        if step_is_successful:
-            out["num_successful_steps"] += 1
-            if x_cost < minimum_cost:
-                minimum_cost = x_cost
-                xbest = x.copy()
-        else:
-            out["num_unsuccessful_steps"] += 1
-        final_cost_min = min(final_cost_min, iter_cost)
-        its.append(dict(iteration=iteration, success=bool(step_is_successful), valid=bool(step_is_valid),
-                        cost=iter_cost, cost_change=cost_change, gradient_max_norm=gmax, step_norm=step_norm,
-                        relative_decrease=rel_decrease, trust_region_radius=radius))
-        out["num_iterations"] = iteration
-        if iteration >= opts.max_num_iterations:
-            term = "NO_CONVERGENCE"
-            message = f"Maximum number of iterations reached. Number of iterations: {iteration}."
-            break
-        if step_is_successful and gmax <= opts.gradient_tolerance:
-            term, message = "CONVERGENCE", "Gradient tolerance reached."
-            break
-        if radius <= opts.min_trust_region_radius:
-            term, message = "CONVERGENCE", "Minimum trust region radius reached."
-            break
-        iteration += 1
-        prev_gmax = gmax
-        step_is_successful = step_is_valid = False
-        cost_change = step_norm = rel_decrease = 0.0
-
-        A, r, g = state["A"], state["r"], state["g"]
-        As = A * scale
-        d = np.clip((As * As).sum(axis=0), opts.min_lm_diagonal, opts.max_lm_diagonal)
-        Dd = np.sqrt(d / radius)
-        H = As.T @ As + np.diag(Dd * Dd)
-        solve_fail = False
-        try:
-            C = np.linalg.cholesky(H)
-            y = np.linalg.solve(C.T, np.linalg.solve(C, g * scale))
-            solve_fail = not np.isfinite(y).all()
-        except np.linalg.LinAlgError:
-            solve_fail = True
-        model_cost_change = 0.0
-        if not solve_fail:
-            delta = -y * scale
-            m = A @ delta
-            model_cost_change = float((-(m * (r + m / 2.0))).sum())
-            step_is_valid = model_cost_change > 0.0
-        if not step_is_valid:
-            num_invalid += 1
-            if num_invalid >= opts.max_num_consecutive_invalid_steps:
-                term = "FAILURE"
-                message = "Number of consecutive invalid steps more than max_num_consecutive_invalid_steps"
-                break
-            radius /= decrease_factor
-            decrease_factor *= 2.0
-            iter_cost, cost_change, gmax = x_cost, 0.0, prev_gmax
-            continue
-        num_invalid = 0
-        xc = x + delta
-        L.unpack(xc, cand)
-        rc, _ = orc.eval_residuals(pkg, cand)
-        candidate_cost = rr.cost(kind, a, rc) if np.isfinite(rc).all() else DBL_MAX
-        step_norm = np.sqrt(((x - xc) ** 2).sum())
-        if step_norm <= opts.parameter_tolerance * (x_norm + opts.parameter_tolerance):
-            term, message = "CONVERGENCE", "Parameter tolerance reached."
-            break
-        cost_change = x_cost - candidate_cost
-        if abs(cost_change) <= opts.function_tolerance * x_cost:
-            term, message = "CONVERGENCE", "Function tolerance reached."
-            break
-        rel_decrease = (x_cost - candidate_cost) / model_cost_change
-        if rel_decrease > opts.min_relative_decrease:
-            x = xc
-            L.unpack(x, work)
-            x_norm = np.sqrt((x * x).sum())
-            x_cost, gmax, ok = evaluate(work)
-            if not ok:
-                term, message = "FAILURE", "Residual and Jacobian evaluation failed."
-                break
-            step_is_successful = True
-            iter_cost = x_cost
-            radius = min(radius / max(1.0 / 3.0, 1.0 - (2.0 * rel_decrease - 1.0) ** 3),
-                         opts.max_trust_region_radius)
-            decrease_factor = 2.0
-        else:
-            step_is_successful = False
-            iter_cost, gmax = candidate_cost, prev_gmax
-            radius /= decrease_factor
-            decrease_factor *= 2.0
-    if minimum_cost < DBL_MAX:
-        L.unpack(xbest, prob)
-    out.setdefault("num_iterations", 0)
-    out.update(termination=term, message=message, final_cost=final_cost_min, iterations=its)
-    return out
 
 
 def scaled_intrinsic_blocks(prob, r, Jz, groups, loss):

@@ -9,15 +9,14 @@ the Y records, S on its three routes, the fixed-point right-hand side, the intri
 back substitutions, the PCG operator and its update kernels, the candidate and model-cost pass)
 is judged on that step, block by block.
 
-The system is the damped, Jacobi-scaled normal equations of robust_ref.lm over the layout of
-ptconst_ref._Layout (which is robust_ref's without a mask and intr_ref's without constant
-points), from the oracle's rows, corrected under a loss: As = A scale,
+The system is the damped, Jacobi-scaled normal equations of lm_ref.lm over lm_ref.Layout, from
+lm_ref.corrected_rows (the oracle's rows and jz's, corrected under a loss): As = A scale,
 d = clip(sum As^2, min_lm_diagonal, max_lm_diagonal) / radius, (As^T As + diag d) y = -As^T r,
 Delta = y scale. It is kept as rows ([2 N][21] values and columns); only 3 x 3 point blocks and
 the camera (+ intrinsic) system are ever dense.
 
 Steps: System.step64() is block elimination and numpy's Cholesky of the reduced system in
-float64 (robust_ref.lm's step up to the summation order); System.refined() adds rounds of
+float64 (lm_ref.lm's step up to the summation order); System.refined() adds rounds of
 iterative refinement with the residual of the full system from the rows in long double, y kept in
 long double, until eta stops falling (eta_ref <= 0.01 eps is asserted for every case on the CPU).
 
@@ -67,6 +66,7 @@ import scipy.sparse as sp
 from scipy.linalg import cho_factor, cho_solve
 
 import intr_ref as ir
+import lm_ref as lr
 import ptconst_ref as pr
 import robust_ref as rr
 
@@ -105,11 +105,10 @@ class System:
     def __init__(self, pkg, orc, prob, radius=1e4, jacobi=1, dmin=1e-6, dmax=1e32, const=None, groups=0,
                  loss=(rr.TRIVIAL, 1.0)):
         self.pkg, self.orc, self.prob, self.loss = pkg, orc, prob, loss
-        L = self.L = pr._Layout(prob, const, groups)
+        L = self.L = lr.Layout(prob, const, groups)
         n = self.n = L.n
-        r, J = orc.eval_jacobians(pkg, prob)
-        assert np.isfinite(r).all() and np.isfinite(J).all()
-        rt, Jt, ps = rr.correct(loss[0], loss[1], r, np.concatenate([J, ir.jz(prob)], axis=2))
+        rt, Jt, ps, ok = lr.corrected_rows(pkg, orc, prob, loss)
+        assert ok and np.isfinite(Jt).all()
         self.cost0 = float(0.5 * ps.astype(LD).sum())
         N = prob.num_obs
         col = np.concatenate([L.col, L.zcol], axis=1)           # [N][21], -1: no column
@@ -219,7 +218,7 @@ class System:
         return np.concatenate([self.LinvT @ (t - self.Y @ yc), yc])
 
     def step64(self):
-        """The float64 step Delta (robust_ref.lm's, up to the summation order)."""
+        """The float64 step Delta (lm_ref.lm's, up to the summation order)."""
         return self.solve64(-self.g64) * self.scale
 
     @functools.lru_cache(maxsize=None)
@@ -341,7 +340,7 @@ class System:
 # ---- schedule facts that depend only on the problem ---------------------------------------------
 def free_cameras_per_point(prob, const=None):
     """[referenced free points] the number of distinct free cameras that see each, in id order."""
-    L = pr._Layout(prob, const, 0)
+    L = lr.Layout(prob, const, 0)
     cam = (L.col[:, [3, 9]] - 3 * L.np) // 6           # free-camera position or negative
     cam = np.where(L.col[:, [3, 9]] >= 0, cam, -1)
     pt = L.col[:, 0] // 3
@@ -352,7 +351,7 @@ def free_cameras_per_point(prob, const=None):
 
 def shared_points(prob, const=None):
     """[nc][nc] the number of free points that two free cameras both see."""
-    L = pr._Layout(prob, const, 0)
+    L = lr.Layout(prob, const, 0)
     _, pairs = free_cameras_per_point(prob, const)
     M = sp.csr_matrix((np.ones(len(pairs)), (pairs[:, 0], pairs[:, 1])), shape=(max(L.np, 1), L.nc))
     return np.asarray((M.T @ M).todense()).astype(np.int64)
@@ -361,7 +360,7 @@ def shared_points(prob, const=None):
 def first_batch_points(prob, single=True):
     """Points of the first batch of the tile route (cut_batches of dab_schur_tables.hip)."""
     m, _ = free_cameras_per_point(prob)
-    cap = batch_cap(pr._Layout(prob).nc, single)
+    cap = batch_cap(lr.Layout(prob).nc, single)
     cur = 0
     for p, k in enumerate(m):
         if p > 0 and (cur + k > cap or p + 1 > BATCH_POINTS):
@@ -456,7 +455,7 @@ def p_bal_1e8(pkg, orc):
 
 def p_near_min(pkg, orc):
     prob = p_bal_small(pkg, orc)[0]
-    s = rr.lm(pkg, orc, prob, pkg.options(max_num_iterations=15, num_threads=4))
+    s = lr.lm(pkg, orc, prob, pkg.options(max_num_iterations=15, num_threads=4))
     # Given 15 iterations the reference stops at its default function tolerance after two (bal-small
     # converges quadratically): gradient 1.7 against 1.3e5 at the start. Fifteen iterations with
     # the tolerances off end at float64's floor (step 7e-12, cost changes below eps cost), where

@@ -12,6 +12,7 @@ import pytest
 import cov_intr_ref as czr
 import cov_ref as cr
 import intr_ref as ir
+import lm_ref as lr
 import robust_ref as rr
 
 LOSSY = [("rig6x20-mixed", "huber"), ("rig6x20-mixed", "cauchy")]
@@ -24,8 +25,8 @@ def jac(pkg, orc):
     def get(name, loss=None):
         if (name, loss) not in cache:
             prob, groups = czr.CASES[name](pkg)
-            cache[(name, loss)] = (prob, groups) + czr.jacobian(pkg, orc, prob, groups,
-                                                                czr.LOSSES[loss] if loss else (rr.TRIVIAL, 1.0))
+            cache[(name, loss)] = (prob, groups) + lr.jacobian(pkg, orc, prob, groups=groups,
+                                                               loss=czr.LOSSES[loss] if loss else (rr.TRIVIAL, 1.0))
         return cache[(name, loss)]
     return get
 
@@ -76,7 +77,7 @@ def test_rank_test_passes_well_posed(jac, name, loss):
 def test_rank_test_flags_gauge_free(pkg, orc):
     """Only arc 0 constant: the scale is free, with or without free intrinsics."""
     for name, prob in (("rig3x5-gauge", cr.rig3x5(pkg, ())), ("shape_a", ir.shape_a(pkg, orc))):
-        L, A, _ = czr.jacobian(pkg, orc, prob, 7)
+        L, A, _ = lr.jacobian(pkg, orc, prob, groups=7)
         t = czr.rank_test(A, L)
         print(f"{name}: camera + z ratio {t['camera_ratio']:.3g}")
         assert len(t["deficient_points"]) == 0

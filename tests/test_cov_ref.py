@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import cov_ref as cr
+import lm_ref as lr
 import robust_ref as rr
 
 LOSSY = [("bal40", (rr.CAUCHY, 0.5)), ("rig6x20", (rr.CAUCHY, 0.5)), ("bal40", (rr.HUBER, 1.0)),
@@ -21,7 +22,7 @@ def jac(pkg, orc):
     def get(name, loss=(rr.TRIVIAL, 1.0)):
         if (name, loss) not in cache:
             prob = {**cr.WELL_POSED, **cr.DEFICIENT}[name](pkg)
-            cache[(name, loss)] = (prob,) + cr.jacobian(pkg, orc, prob, loss)
+            cache[(name, loss)] = (prob,) + lr.jacobian(pkg, orc, prob, loss=loss)
         return cache[(name, loss)]
     return get
 
@@ -68,7 +69,7 @@ def test_rank_test_flags_gauge_free(jac, name):
 
 def test_rank_test_flags_single_observation_points(pkg, orc):
     prob, _ = rr.bal_small(pkg, orc, contaminated=False)
-    L, A, _ = cr.jacobian(pkg, orc, prob)
+    L, A, _ = lr.jacobian(pkg, orc, prob)
     t = cr.rank_test(A, L)
     single = np.flatnonzero(np.bincount(prob.obs_point, minlength=prob.points.shape[0]) == 1)
     assert len(single) > 0

@@ -22,6 +22,7 @@ import pytest
 import cov_intr_ref as czr
 import cov_ref as cr
 import intr_ref as ir
+import lm_ref as lr
 import robust_ref as rr
 
 pytestmark = pytest.mark.gpu
@@ -39,7 +40,7 @@ def case(pkg, orc, name, loss=None):
     key = (name, loss)
     if key not in _cache:
         prob, groups = czr.CASES[name](pkg)
-        ref = czr.reference(pkg, orc, prob, groups, czr.LOSSES[loss] if loss else (rr.TRIVIAL, 1.0))
+        ref = lr.covariance(pkg, orc, prob, groups=groups, loss=czr.LOSSES[loss] if loss else (rr.TRIVIAL, 1.0))
         _cache[key] = (prob, groups, ref)
     return _cache[key]
 

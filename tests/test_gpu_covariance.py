@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import cov_ref as cr
+import lm_ref as lr
 import robust_ref as rr
 
 pytestmark = pytest.mark.gpu
@@ -32,7 +33,7 @@ def case(pkg, orc, name, loss=None):
     key = (name, loss)
     if key not in _cache:
         prob = cr.WELL_POSED[name.replace("-pairs", "")](pkg)
-        _cache[key] = (prob, cr.reference(pkg, orc, prob, LOSSES[loss] if loss else (rr.TRIVIAL, 1.0)))
+        _cache[key] = (prob, lr.covariance(pkg, orc, prob, loss=LOSSES[loss] if loss else (rr.TRIVIAL, 1.0)))
     return _cache[key]
 
 

@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 import intr_ref as ir
+import lm_ref as lr
 import robust_ref as rr
 from golden_util import TOL_JAC
 
@@ -45,13 +46,13 @@ _ref_cache = {}
 
 
 def reference(pkg, orc, shapes, shape, groups, loss=None, iters=15):
-    """intr_ref.lm on a copy of the shape, computed once per case."""
+    """lm_ref.lm on a copy of the shape, computed once per case."""
     key = (shape, groups, loss, iters)
     if key not in _ref_cache:
         p = shapes[shape].copy()
         o = pkg.options(max_num_iterations=iters, num_threads=4,
                         linear_solver_type=pkg.DAB_LINEAR_SOLVER_EXPLICIT_SCHUR)
-        _ref_cache[key] = (ir.lm(pkg, orc, p, o, groups, LOSS_REF[loss]), p)
+        _ref_cache[key] = (lr.lm(pkg, orc, p, o, groups=groups, loss=LOSS_REF[loss]), p)
     return _ref_cache[key]
 
 

@@ -15,6 +15,7 @@ import pytest
 
 import cov_ref as cr
 import intr_ref as ir
+import lm_ref as lr
 import prior_ref as qr
 import ptconst_ref as pr
 import robust_ref as rr
@@ -64,13 +65,14 @@ _ref = {}
 
 
 def reference(pkg, orc, key, make, iters, const=None, loss=None, groups=0):
-    """(summary, solved problem, start, priors, mask) of prior_ref.lm, once per key, never modified.
+    """(summary, solved problem, start, priors, mask) of lm_ref.lm, once per key, never modified.
     make() -> (problem, priors)."""
     if key not in _ref:
         start, priors = make()
         p = start.copy()
         m = pr.MASKS[const](p) if isinstance(const, str) else const
-        _ref[key] = (qr.lm(pkg, orc, p, _opts(pkg, iters), priors, m, groups, loss or TRIVIAL), p, start, priors, m)
+        _ref[key] = (lr.lm(pkg, orc, p, _opts(pkg, iters), priors=priors, const=m, groups=groups, loss=loss or TRIVIAL), p, start,
+                     priors, m)
     return _ref[key]
 
 
@@ -498,7 +500,7 @@ def test_position_priors_fix_the_gauge(pkg, orc, gpu, name):
     priors = qr.pos3(prob, seed=3)
     free, _ = _cov(pkg, prob.copy(), None)
     assert free["info"]["status"] == "RANK_DEFICIENT" and free["point_cov"] is None
-    ref = qr.covariance(pkg, orc, prob, priors)
+    ref = lr.covariance(pkg, orc, prob, priors=priors)
     assert not ref["rank"]["deficient"] and ref["num_effective"] == 3
     g, traj = _cov(pkg, prob.copy(), priors, solve_after=5)
     _check_cov(name + "/pos3", g, ref, "ext_full")
@@ -511,7 +513,7 @@ def test_position_priors_fix_the_gauge(pkg, orc, gpu, name):
 def test_covariance_intrinsics_with_pose_priors(pkg, orc, gpu):
     prob = ir.shape_a(pkg, orc)
     priors = qr.pose(prob, seed=3)
-    ref = qr.covariance(pkg, orc, prob, priors, None, 7)
+    ref = lr.covariance(pkg, orc, prob, priors=priors, groups=7)
     assert not ref["rank"]["deficient"]
     g, traj = _cov(pkg, prob.copy(), priors, 7, solve_after=5)
     _check_cov("shape_a/groups 7/pose", g, ref, "cam_full")

@@ -15,6 +15,7 @@ import pytest
 
 import cov_ref as cr
 import intr_ref as ir
+import lm_ref as lr
 import ptconst_ref as pr
 import robust_ref as rr
 
@@ -56,12 +57,12 @@ _ref = {}
 
 
 def reference(pkg, orc, key, make, mask, iters, loss=None, groups=0):
-    """(summary, solved problem, start, mask) of ptconst_ref.lm, computed once per key, never modified."""
+    """(summary, solved problem, start, mask) of lm_ref.lm, computed once per key, never modified."""
     if key not in _ref:
         start = make()
         p = start.copy()
         m = pr.MASKS[mask](p) if isinstance(mask, str) else mask
-        _ref[key] = (pr.lm(pkg, orc, p, _opts(pkg, iters), m, groups, loss or TRIVIAL), p, start, m)
+        _ref[key] = (lr.lm(pkg, orc, p, _opts(pkg, iters), const=m, groups=groups, loss=loss or TRIVIAL), p, start, m)
     return _ref[key]
 
 
@@ -239,7 +240,7 @@ def test_no_free_parameter(pkg, orc, gpu, lst):
     which = {"explicit": pkg.DAB_LINEAR_SOLVER_EXPLICIT_SCHUR, "pcg": pkg.DAB_LINEAR_SOLVER_IMPLICIT_SCHUR_PCG,
              "auto": pkg.DAB_LINEAR_SOLVER_AUTO}[lst]
     g = gpu_solve(pkg, prob, True, 25, lst=which)
-    o = pr.lm(pkg, orc, start.copy(), _opts(pkg, 25), True)
+    o = lr.lm(pkg, orc, start.copy(), _opts(pkg, 25), const=True)
     assert (g["termination"], g["num_iterations"], g["iterations"]) == ("CONVERGENCE", 0, [])
     assert g["message"] == o["message"] == "Function tolerance reached. No non-constant parameter blocks found."
     assert g["initial_cost"] == g["final_cost"] == pytest.approx(o["initial_cost"], rel=1e-12)
@@ -398,7 +399,7 @@ def test_one_constant_point_fixes_the_gauge(pkg, orc, gpu, name):
     m[0] = True
     free, _ = _cov(pkg, prob.copy(), None)
     assert free["info"]["status"] == "RANK_DEFICIENT" and free["point_cov"] is None
-    ref = pr.covariance(pkg, orc, prob, m)
+    ref = lr.covariance(pkg, orc, prob, const=m)
     assert not ref["rank"]["deficient"]
     g, traj = _cov(pkg, prob.copy(), m, solve_first=5)
     _check_cov(name + "/point 0 constant", g, ref, "ext_full")
@@ -411,7 +412,7 @@ def test_one_constant_point_fixes_the_gauge(pkg, orc, gpu, name):
 def test_covariance_all_points_constant(pkg, orc, gpu):
     """Sigma_cc = U^-1, blockwise for a BAL shape (the general masked route: S = U)."""
     prob = cr.bal40(pkg, ())
-    ref = pr.covariance(pkg, orc, prob, True)
+    ref = lr.covariance(pkg, orc, prob, const=True)
     g, _ = _cov(pkg, prob.copy(), True)
     _check_cov("bal40/all constant", g, ref, "ext_full")
     ref_pts = np.where(np.isnan(ref["point_cov"]), np.nan, 0.0)
@@ -443,7 +444,7 @@ def test_covariance_intrinsics_with_a_constant_point(pkg, orc, gpu):
     assert prob.intr.shape[0] == 6
     m = np.zeros(prob.points.shape[0], bool)
     m[0] = True
-    ref = pr.covariance(pkg, orc, prob, m, groups)
+    ref = lr.covariance(pkg, orc, prob, const=m, groups=groups)
     assert not ref["rank"]["deficient"]
     g, _ = _cov(pkg, prob.copy(), m, groups)
     _check_cov("rig6x20/mixed free set/point 0 constant", g, ref, "cam_full")

@@ -20,6 +20,7 @@ import sys
 import numpy as np
 import pytest
 
+import lm_ref as lr
 import robust_ref as rr
 from golden_util import GOLDEN
 
@@ -40,14 +41,14 @@ _ref_cache = {}
 
 
 def reference(pkg, orc, shapes, shape, loss, freeze=False, iters=15):
-    """robust_ref.lm on a copy of the shape, computed once per case."""
+    """lm_ref.lm on a copy of the shape, computed once per case."""
     key = (shape, loss, freeze, iters)
     if key not in _ref_cache:
         p = shapes[shape][0].copy()
         p.freeze_camera = freeze
         opts = pkg.options(max_num_iterations=iters, num_threads=4,
                            linear_solver_type=pkg.DAB_LINEAR_SOLVER_EXPLICIT_SCHUR)
-        _ref_cache[key] = (rr.lm(pkg, orc, p, opts, LOSSES[loss]), p)
+        _ref_cache[key] = (lr.lm(pkg, orc, p, opts, loss=LOSSES[loss]), p)
     return _ref_cache[key]
 
 
@@ -126,7 +127,7 @@ def test_blocks_and_cost_under_loss(pkg, orc, gpu, shapes, shape, loss, fused, p
         assert abs(b["ux"].sum() - ref["cross"]) <= 1e-9 * np.abs(b["ux"]).sum()
 
 
-# ---- 5. LM trajectory against robust_ref.lm ----------------------------------------------------
+# ---- 5. LM trajectory against lm_ref.lm --------------------------------------------------------
 @pytest.mark.parametrize("freeze", [False, True])
 @pytest.mark.parametrize("loss", ["huber", "cauchy"])
 @pytest.mark.parametrize("shape", ["bal", "rig"])
@@ -299,14 +300,14 @@ def test_refusals(pkg, gpu, shapes):
 
 # ---- 10. it is robust --------------------------------------------------------------------------
 def test_cauchy_recovers_the_inliers(pkg, orc, gpu):
-    ra, rb, rc = rr.robust_triplet(pkg, orc)
+    ra, rb, rc = lr.robust_triplet(pkg, orc)
     assert ra <= rc < rb, (ra, rc, rb)  # the premise, on the reference alone
 
     def solve(p, loss):
         names = {rr.TRIVIAL: None, rr.CAUCHY: CAUCHY}
         gpu_solve(pkg, p, names[loss[0]], "explicit", iters=25)
 
-    ga, gb, gc = rr.robust_triplet(pkg, orc, solve)
+    ga, gb, gc = lr.robust_triplet(pkg, orc, solve)
     assert gc == pytest.approx(rc, rel=1e-6)
     assert ga <= gc < gb, (ga, gc, gb)
 

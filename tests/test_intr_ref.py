@@ -1,5 +1,5 @@
-"""CPU tests of the free-intrinsics reference (tests/intr_ref.py) and of the part of the C ABI
-that needs no device. The GPU tests (test_gpu_intrinsics.py) trust intr_ref.jz / intr_ref.lm
+"""CPU tests of the free-intrinsics reference (tests/intr_ref.py, tests/lm_ref.py) and of the part
+of the C ABI that needs no device. The GPU tests (test_gpu_intrinsics.py) trust intr_ref.jz / lm_ref.lm
 only because these pin them: the analytic intrinsic columns against central differences of the
 oracle's residual, the LM loop against the oracle at groups = 0, and, on the shapes the GPU
 tests use, that the reference itself behaves (lower cost with the intrinsics free, the same
@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import intr_ref as ir
+import lm_ref as lr
 import robust_ref as rr
 
 
@@ -70,7 +71,7 @@ def _same(a, o, pa, po):
 @pytest.mark.parametrize("shape", ["a", "b"])
 def test_lm_with_no_group_reproduces_oracle(pkg, orc, shapes, shape):
     pa, po = shapes[shape].copy(), shapes[shape].copy()
-    a = ir.lm(pkg, orc, pa, _opts(pkg), 0)
+    a = lr.lm(pkg, orc, pa, _opts(pkg), groups=0)
     o = orc.solve(pkg, po, _opts(pkg))
     assert len(o["iterations"]) > 3
     _same(a, o, pa, po)
@@ -84,7 +85,7 @@ def _lm(pkg, orc, shapes, shape, groups, order=0):
     key = (shape, groups, order)
     if key not in _lm_cache:
         p = shapes[shape].copy() if order == 0 else ir.reorder(shapes[shape])
-        _lm_cache[key] = (ir.lm(pkg, orc, p, _opts(pkg), groups), p)
+        _lm_cache[key] = (lr.lm(pkg, orc, p, _opts(pkg), groups=groups), p)
     return _lm_cache[key]
 
 
@@ -114,7 +115,7 @@ ORDER_COST_BOUND = {("b", 7): 1.1e-9}
 @pytest.mark.parametrize("shape,groups", [("a", 7), ("b", 7), ("c", 7), ("a", 2), ("b", 5), ("c", 2)])
 def test_two_observation_orders_agree(pkg, orc, shapes, shape, groups):
     """What entitles the GPU tests to the project's bounds (LM cost 1e-9 relative, parameters
-    1e-7): intr_ref.lm on two listings of the same problem (the given order and its reverse)
+    1e-7): lm_ref.lm on two listings of the same problem (the given order and its reverse)
     gives the same records, every iteration's cost within 1e-10 relative and parameters within
     1e-8.
     Measured, max over the iteration records of |cost difference| / cost, then intrinsics

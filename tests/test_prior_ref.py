@@ -1,6 +1,9 @@
-"""Pins tests/prior_ref.py, the reference of the extrinsic-prior tests (CPU only).
+"""Pins tests/lm_ref.py with priors, the reference of the extrinsic-prior tests, on the prior sets
+and cases of tests/prior_ref.py (CPU only).
 
-  * with no priors its lm() is ptconst_ref.lm, record for record and bit for bit;
+  * with no priors, and with a prior on a constant extrinsic alone, lm() is lm() without the
+    argument, record for record and bit for bit (what the loop without the feature returned is
+    pinned by tests/test_lm_ref.py);
   * the gradient's camera part equals central differences of the reference's cost (1e-6);
   * the reference's own spread: on every trajectory case of the GPU tests, the given observation
     order and its reverse (intr_ref.reorder) give the same records, every iteration's cost within
@@ -17,6 +20,7 @@ import pytest
 
 import cov_ref as cr
 import intr_ref as ir
+import lm_ref as lr
 import prior_ref as qr
 import ptconst_ref as pr
 import robust_ref as rr
@@ -35,7 +39,8 @@ def _lm(pkg, orc, t, order=0, with_priors=True):
     if key not in _cache:
         base, priors, m, loss, groups, iters = qr.make_case(pkg, orc, t)
         p = base.copy() if order == 0 else ir.reorder(base)
-        out = qr.lm(pkg, orc, p, _opts(pkg, iters), priors if with_priors else None, m, groups, loss)
+        out = lr.lm(pkg, orc, p, _opts(pkg, iters), priors=priors if with_priors else None, const=m, groups=groups,
+                    loss=loss)
         _cache[key] = (out, p, base)
     return _cache[key]
 
@@ -45,8 +50,8 @@ def test_no_priors_is_ptconst_ref(pkg, orc, case, mask, loss):
     loss = loss or (rr.TRIVIAL, 1.0)
     pa, pb, pc = (pr.CASES[case](pkg) for _ in range(3))
     m = pr.MASKS[mask](pa) if mask else None
-    a = pr.lm(pkg, orc, pa, _opts(pkg, 8), m, 0, loss)
-    b = qr.lm(pkg, orc, pb, _opts(pkg, 8), None, m, 0, loss)
+    a = lr.lm(pkg, orc, pa, _opts(pkg, 8), const=m, loss=loss)
+    b = lr.lm(pkg, orc, pb, _opts(pkg, 8), priors=None, const=m, loss=loss)
     assert a == b                       # every record and every summary field, bit for bit
     assert len(a["iterations"]) > 3
     np.testing.assert_array_equal(pa.points, pb.points)
@@ -54,7 +59,7 @@ def test_no_priors_is_ptconst_ref(pkg, orc, case, mask, loss):
     # a prior on a constant extrinsic alone (camera 0 / arc 0) is skipped entirely
     only_const = (np.array([0], np.int32), np.ones((1, 6)), np.eye(6)[None])
     assert pc.ext_const[0]
-    c = qr.lm(pkg, orc, pc, _opts(pkg, 8), only_const, m, 0, loss)
+    c = lr.lm(pkg, orc, pc, _opts(pkg, 8), priors=only_const, const=m, loss=loss)
     assert a == c
 
 
@@ -62,15 +67,15 @@ def test_no_priors_is_ptconst_ref(pkg, orc, case, mask, loss):
 def test_gradient_is_central_differences_of_the_cost(pkg, orc, case, pset):
     prob = pr.CASES[case](pkg)
     priors = qr.PRIORS[pset](prob)
-    L, cost, g = qr.cost_and_gradient(pkg, orc, prob, priors)
+    L, cost, g = lr.cost_and_gradient(pkg, orc, prob, priors=priors)
     gc = g[3 * L.np:].reshape(-1, 6)
     # the priors' own part (the observations' gradient is ~1e7 times larger and would hide it)
     # against the same differences of the priors' cost alone
-    gp = gc - qr.cost_and_gradient(pkg, orc, prob, None)[2][3 * L.np:].reshape(-1, 6)
-    eff = qr.effective(L, priors)
+    gp = gc - lr.cost_and_gradient(pkg, orc, prob, priors=None)[2][3 * L.np:].reshape(-1, 6)
+    eff = lr.effective(L, priors)
 
     def pcost(p):
-        r = qr.prior_residuals(L, eff, p)
+        r = lr.prior_residuals(L, eff, p)
         return 0.5 * (r * r).sum()
     h = 1e-6
     worst = worst_p = 0.0
@@ -80,7 +85,8 @@ def test_gradient_is_central_differences_of_the_cost(pkg, orc, case, pset):
             hi, lo = prob.copy(), prob.copy()
             hi.ext[L.ext_of[c], k] += h
             lo.ext[L.ext_of[c], k] -= h
-            fd = (qr.cost_and_gradient(pkg, orc, hi, priors)[1] - qr.cost_and_gradient(pkg, orc, lo, priors)[1]) / (2 * h)
+            fd = (lr.cost_and_gradient(pkg, orc, hi, priors=priors)[1]
+                  - lr.cost_and_gradient(pkg, orc, lo, priors=priors)[1]) / (2 * h)
             fd_p = (pcost(hi) - pcost(lo)) / (2 * h)
             worst = max(worst, abs(fd - gc[c, k]) / max(1.0, abs(gc[c, k])))
             worst_p = max(worst_p, abs(fd_p - gp[c, k]) / max(1.0, abs(gp[c, k])))
@@ -132,10 +138,10 @@ def test_rejected_steps_where_the_gpu_tests_rely_on_them(pkg, orc):
 @pytest.mark.parametrize("name", ["bal40", "rig3x5"])
 def test_position_priors_fix_the_gauge(pkg, orc, name):
     prob = cr.bal40(pkg, ()) if name == "bal40" else cr.rig3x5(pkg, ())
-    free = qr.covariance(pkg, orc, prob, None)
-    three = qr.covariance(pkg, orc, prob, qr.pos3(prob, seed=3))
+    free = lr.covariance(pkg, orc, prob, priors=None)
+    three = lr.covariance(pkg, orc, prob, priors=qr.pos3(prob, seed=3))
     L = three["layout"]
-    one = qr.covariance(pkg, orc, prob, qr.pos3(prob, seed=3, which=[L.ext_of[len(L.ext_of) // 2]]))
+    one = lr.covariance(pkg, orc, prob, priors=qr.pos3(prob, seed=3, which=[L.ext_of[len(L.ext_of) // 2]]))
     print(name, "camera ratio", free["rank"]["camera_ratio"], "-> pos3", three["rank"]["camera_ratio"], "kappa",
           three["kappa"], "one prior alone", one["rank"]["camera_ratio"])
     assert free["rank"]["deficient"]
@@ -144,9 +150,9 @@ def test_position_priors_fix_the_gauge(pkg, orc, name):
     assert three["kappa"] < 1e8
     assert three["num_residuals"] == free["num_residuals"] + 18 and three["num_parameters"] == free["num_parameters"]
     assert three["cost"] > free["cost"]
-    # no priors: ptconst_ref.covariance bit for bit
+    # no priors: the covariance without the argument bit for bit
     well = cr.bal40(pkg) if name == "bal40" else cr.rig3x5(pkg)
-    a, b = pr.covariance(pkg, orc, well, None), qr.covariance(pkg, orc, well, None)
+    a, b = lr.covariance(pkg, orc, well, const=None), lr.covariance(pkg, orc, well, priors=None)
     for k in ("point_cov", "ext_cov", "cam_full"):
         np.testing.assert_array_equal(a[k], b[k])
 

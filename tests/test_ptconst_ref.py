@@ -1,6 +1,8 @@
-"""Pins tests/ptconst_ref.py, the reference of the constant-point tests (CPU only).
+"""Pins tests/lm_ref.py with constant points, the reference of the constant-point tests, on the
+cases of tests/ptconst_ref.py (CPU only).
 
-  * with an empty mask its lm() is robust_ref.lm, record for record and bit for bit;
+  * with an empty mask lm() is lm() without a mask, record for record and bit for bit (what the
+    loop without the feature returned is pinned by tests/test_lm_ref.py);
   * constant points never move, and their count leaves num_parameters / num_free_points;
   * the reference's own spread: on every case of the GPU trajectory test, the given observation
     order and its reverse (intr_ref.reorder) give the same records, every iteration's cost within
@@ -17,6 +19,7 @@ import pytest
 
 import cov_ref as cr
 import intr_ref as ir
+import lm_ref as lr
 import ptconst_ref as pr
 import robust_ref as rr
 
@@ -36,7 +39,7 @@ def _lm(pkg, orc, t, order=0):
         base = pr.CASES[case](pkg)
         p = base.copy() if order == 0 else ir.reorder(base)
         m = pr.MASKS[mask](p)
-        out = pr.lm(pkg, orc, p, _opts(pkg, iters), m, 0, loss or (rr.TRIVIAL, 1.0))
+        out = lr.lm(pkg, orc, p, _opts(pkg, iters), const=m, loss=loss or (rr.TRIVIAL, 1.0))
         _cache[key] = (out, p, base, m)
     return _cache[key]
 
@@ -45,8 +48,8 @@ def _lm(pkg, orc, t, order=0):
 def test_empty_mask_is_robust_ref(pkg, orc, case, loss):
     loss = loss or (rr.TRIVIAL, 1.0)
     pa, pb = pr.CASES[case](pkg), pr.CASES[case](pkg)
-    a = rr.lm(pkg, orc, pa, _opts(pkg, 8), loss)
-    b = pr.lm(pkg, orc, pb, _opts(pkg, 8), np.zeros(pb.points.shape[0], bool), 0, loss)
+    a = lr.lm(pkg, orc, pa, _opts(pkg, 8), loss=loss)
+    b = lr.lm(pkg, orc, pb, _opts(pkg, 8), const=np.zeros(pb.points.shape[0], bool), loss=loss)
     assert a == b                       # every record and every summary field, bit for bit
     assert len(a["iterations"]) > 3
     np.testing.assert_array_equal(pa.points, pb.points)
@@ -91,12 +94,12 @@ def test_free_intrinsics_layout(pkg, orc):
     """Constant points beside free intrinsics: the intrinsic columns keep every observation."""
     prob = ir.shape_a(pkg, orc)
     m = pr.every_third(prob)
-    L0, L = ir._Layout(prob, 7), pr._Layout(prob, m, 7)
+    L0, L = lr.Layout(prob, None, 7), lr.Layout(prob, m, 7)
     assert (L.np, L.nc, L.nz) == (L0.np - int(m[L0.pt_of].sum()), L0.nc, L0.nz)
     assert (L.zcol >= 0).sum() == (L0.zcol >= 0).sum()
     assert (L.col[m[prob.obs_point], :3] == -1).all() and (L.col[~m[prob.obs_point], :3] >= 0).all()
     base = prob.copy()
-    out = pr.lm(pkg, orc, prob, _opts(pkg, 6), m, 7)
+    out = lr.lm(pkg, orc, prob, _opts(pkg, 6), const=m, groups=7)
     np.testing.assert_array_equal(prob.points[m], base.points[m])
     assert out["num_parameters"] == L.n and np.abs(prob.intr - base.intr).max() > 1e-3
 
@@ -105,9 +108,9 @@ def test_no_free_parameter(pkg, orc):
     prob = pr.case_b(pkg)
     prob.freeze_camera = True
     base = prob.copy()
-    out = pr.lm(pkg, orc, prob, _opts(pkg), True)
+    out = lr.lm(pkg, orc, prob, _opts(pkg), const=True)
     assert (out["termination"], out["num_iterations"], out["iterations"]) == ("CONVERGENCE", 0, [])
-    assert out["message"] == pr.NO_FREE_MESSAGE and out["initial_cost"] == out["final_cost"] > 0.0
+    assert out["message"] == lr.NO_FREE_MESSAGE and out["initial_cost"] == out["final_cost"] > 0.0
     assert out["num_parameters"] == 0
     np.testing.assert_array_equal(prob.points, base.points)
     np.testing.assert_array_equal(prob.ext, base.ext)
@@ -115,13 +118,13 @@ def test_no_free_parameter(pkg, orc):
 
 def test_covariance_blocks_and_gauge(pkg, orc):
     """One constant point takes the gauge-free problems from deficient to well conditioned, and
-    its row of point_cov is exactly 0; an empty mask is cov_ref.reference."""
+    its row of point_cov is exactly 0; an empty mask is no mask."""
     for name, make in (("bal40", lambda: cr.bal40(pkg, ())), ("rig3x5", lambda: cr.rig3x5(pkg, ()))):
         prob = make()
         m = np.zeros(prob.points.shape[0], bool)
-        free = pr.covariance(pkg, orc, prob, None)
+        free = lr.covariance(pkg, orc, prob, const=None)
         m[0] = True
-        one = pr.covariance(pkg, orc, prob, m)
+        one = lr.covariance(pkg, orc, prob, const=m)
         print(name, "camera ratio", free["rank"]["camera_ratio"], "->", one["rank"]["camera_ratio"], "kappa",
               free["kappa"], "->", one["kappa"])
         assert free["rank"]["deficient"] and not one["rank"]["deficient"]
@@ -129,12 +132,12 @@ def test_covariance_blocks_and_gauge(pkg, orc):
         assert (one["point_cov"][0] == 0.0).all() and np.isfinite(one["point_cov"][1:]).all()
         assert one["num_parameters"] == free["num_parameters"] - 3
     prob = cr.bal40(pkg)
-    a, b = cr.reference(pkg, orc, prob), pr.covariance(pkg, orc, prob, None)
+    a, b = lr.covariance(pkg, orc, prob), lr.covariance(pkg, orc, prob, const=None)
     for k in ("point_cov", "ext_cov"):
         np.testing.assert_array_equal(a[k], b[k])
     np.testing.assert_array_equal(a["ext_full"], b["cam_full"])
     # every point constant: Sigma_cc is blockwise U^-1 for a BAL shape
-    allc = pr.covariance(pkg, orc, prob, True)
+    allc = lr.covariance(pkg, orc, prob, const=True)
     off = allc["cam_full"].copy()
     for c in range(allc["ext_cov"].shape[0]):
         off[6 * c:6 * c + 6, 6 * c:6 * c + 6] = 0.0

@@ -1,5 +1,5 @@
-"""CPU tests of the robust-loss reference (tests/robust_ref.py) and of the part of the C ABI
-that needs no device. The GPU tests (test_gpu_robust.py) trust robust_ref.lm only because
+"""CPU tests of the robust-loss reference (tests/robust_ref.py, tests/lm_ref.py) and of the part of
+the C ABI that needs no device. The GPU tests (test_gpu_robust.py) trust lm_ref.lm only because
 these pin it: the loss table against finite differences, and the LM loop against the oracle
 (orc_solve, the DENSE_SCHUR restatement) at the TRIVIAL loss."""
 import ctypes as C
@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import lm_ref as lr
 import robust_ref as rr
 
 LOSSES = [(rr.HUBER, 1.0), (rr.SOFT_L1, 1.0), (rr.CAUCHY, 0.5), (rr.HUBER, 2.5), (rr.CAUCHY, 3.0)]
@@ -69,7 +70,7 @@ def test_trivial_lm_reproduces_oracle(pkg, orc, case):
     opts = pkg.options(max_num_iterations=15, num_threads=4, function_tolerance=1e-12,
                        linear_solver_type=pkg.DAB_LINEAR_SOLVER_EXPLICIT_SCHUR)
     pa, po = prob.copy(), prob.copy()
-    a = rr.lm(pkg, orc, pa, opts)
+    a = lr.lm(pkg, orc, pa, opts)
     o = orc.solve(pkg, po, opts)
     assert len(o["iterations"]) > 3
     _same(a, o, pa, po)
@@ -100,5 +101,5 @@ def test_robust_ordering_on_the_cpu(pkg, orc):
     """The premise of the GPU robustness test, on the reference alone: inlier RMS after a
     solve of (a) clean data, no loss <= (c) contaminated, Cauchy(0.5) < (b) contaminated, no
     loss."""
-    a, b, c = rr.robust_triplet(pkg, orc)
+    a, b, c = lr.robust_triplet(pkg, orc)
     assert a <= c < b, (a, c, b)

@@ -1,14 +1,12 @@
 """Pins tests/step_ref.py (the reference of tests/test_gpu_step.py) on the CPU: the refined step
-solves every case's system to eta_ref <= 0.01 eps, the float64 step is the one of the three
-reference LMs, and every GPU case meets the conditions it relies on (first step accepted, the
+solves every case's system to eta_ref <= 0.01 eps, the float64 step is the one of the
+reference LM (lm_ref.lm), and every GPU case meets the conditions it relies on (first step accepted, the
 schedule facts that depend only on the problem, at least 21 CG iterations for the PCG cases).
 Every case runs here, the 2600-point one included (its system takes a fraction of a second)."""
 import numpy as np
 import pytest
 
-import intr_ref as ir
-import ptconst_ref as pr
-import robust_ref as rr
+import lm_ref as lr
 import step_ref as sr
 
 UNIQUE = list({c.key: c for c in reversed(sr.CASES)}.values())[::-1]  # the first case of every system
@@ -60,12 +58,7 @@ def test_float64_step_is_the_reference_lm_step(pkg, orc, name):
     S = sr.System(pkg, orc, prob.copy(), radius=1.0, const=const, groups=groups, loss=loss)
     p = prob.copy()
     o = _one_iteration(pkg, initial_trust_region_radius=1.0)
-    if name == "bal_small":
-        s = rr.lm(pkg, orc, p, o, loss)
-    elif name == "shape_a":
-        s = ir.lm(pkg, orc, p, o, groups, loss)
-    else:
-        s = pr.lm(pkg, orc, p, o, const, groups, loss)
+    s = lr.lm(pkg, orc, p, o, const=const, groups=groups, loss=loss)
     assert s["iterations"][1]["success"] and s["num_parameters"] == S.n
     got, want = S.observed(p), S.channel(S.step64())
     err = np.linalg.norm(got - want) / np.linalg.norm(want)
