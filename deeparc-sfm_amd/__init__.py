@@ -11,8 +11,8 @@ from ._abi import (DAB_CONVERGENCE, DAB_E_INVALID, DAB_E_UNSUPPORTED, DAB_FAILUR
 from ._abi import DabCovarianceInfo, DabCovarianceIntrInfo, DabCovarianceOptions
 from ._abi import DAB_INTR_CENTER, DAB_INTR_DISTORTION, DAB_INTR_FOCAL
 from ._abi import DAB_SCHUR_DIRECT, DAB_SCHUR_PAIRS, DAB_SCHUR_TILES
-from .core import (CONFIGS, Problem, Solver, covariance_options, options, solve, sqrt_info_from_sigmas, synth,
-                   synth_config)
+from .core import (CONFIGS, Problem, Solver, covariance_options, options, point_sqrt_info_from_sigmas, solve,
+                   sqrt_info_from_sigmas, synth, synth_config)
 
 __all__ = [
     "CONFIGS", "Problem", "Solver", "options", "solve", "synth", "synth_config",
@@ -24,5 +24,5 @@ __all__ = [
     "DAB_E_INVALID", "DAB_E_UNSUPPORTED",
     "DAB_INTR_CENTER", "DAB_INTR_FOCAL", "DAB_INTR_DISTORTION",
     "DAB_SCHUR_PAIRS", "DAB_SCHUR_TILES", "DAB_SCHUR_DIRECT",
-    "sqrt_info_from_sigmas",
+    "sqrt_info_from_sigmas", "point_sqrt_info_from_sigmas",
 ]

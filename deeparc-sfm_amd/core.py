@@ -79,6 +79,19 @@ class Problem:
         owner = self.point_owner(world)
         return self.subset(owner[self.obs_point] == rank)
 
+    def shard_point_priors(self, point_priors, rank, world):
+        """The part of a global point-prior set (index, mean, sqrt_info) that belongs to `rank`:
+        the priors on the points that rank owns (point ids are global on a shard). What that rank
+        passes to Solver.set_point_priors on the handle of shard(rank, world)."""
+        idx, mu, a = point_priors
+        idx = np.asarray(idx, np.int32).reshape(-1)
+        mu = np.asarray(mu, np.float64).reshape(-1, 3)
+        a = np.asarray(a, np.float64).reshape(-1, 3, 3)
+        if world <= 1:
+            return idx, mu, a
+        keep = self.point_owner(world)[idx] == rank
+        return idx[keep], mu[keep], a[keep]
+
     def as_c(self):
         """dab_problem view of the arrays (valid while self is alive)."""
         p = DabProblem()
@@ -359,6 +372,47 @@ class Solver:
         check(self.lib.dab_eval_ext_priors(self.h, _ptr(r, C.c_double), C.byref(cost)), self.lib)
         return r, cost.value
 
+    def set_point_priors(self, index, mean=None, sqrt_info=None):
+        """Gaussian priors on points (dab_set_point_priors; Ceres' NormalPrior(A, mu) with a NULL
+        loss on the point's block): index [n] point ids, mean [n][3], sqrt_info [n][3][3] = A of the
+        residual A (X - mean). None or an empty index clears them. Set after set_problem, which
+        resets them; they survive update_parameters, set_loss, the masks and set_ext_priors. A
+        prior on a constant or unreferenced point is ignored. On a multi-rank handle each rank
+        sets the priors of its own shard's points (Problem.shard_point_priors)."""
+        if index is None or np.size(index) == 0:
+            check(self.lib.dab_set_point_priors(self.h, 0, None, None, None), self.lib)
+            return
+        idx = np.ascontiguousarray(index, np.int32).reshape(-1)
+        n = idx.shape[0]
+        mu = np.ascontiguousarray(mean, np.float64)
+        a = np.ascontiguousarray(sqrt_info, np.float64)
+        if mu.shape != (n, 3) or a.shape != (n, 3, 3):
+            raise ValueError(f"mean: ({n}, 3) and sqrt_info: ({n}, 3, 3) values")
+        check(self.lib.dab_set_point_priors(self.h, n, _ptr(idx, C.c_int32), _ptr(mu, C.c_double),
+                                            _ptr(a, C.c_double)), self.lib)
+
+    def get_point_priors(self):
+        """(index [n], mean [n][3], sqrt_info [n][3][3], num_effective) as set."""
+        n, ne = C.c_int32(), C.c_int32()
+        check(self.lib.dab_get_point_priors(self.h, C.byref(n), C.byref(ne), None, None, None), self.lib)
+        idx = np.zeros(n.value, np.int32)
+        mu = np.zeros((n.value, 3))
+        a = np.zeros((n.value, 3, 3))
+        check(self.lib.dab_get_point_priors(self.h, None, None, _ptr(idx, C.c_int32), _ptr(mu, C.c_double),
+                                            _ptr(a, C.c_double)), self.lib)
+        return idx, mu, a, ne.value
+
+    def eval_point_priors(self):
+        """(residuals [n][3] in the order set, cost = 0.5 sum |r|^2 over this rank's effective
+        priors) at the parameters on the handle (dab_eval_point_priors); an ignored prior's row
+        is zero."""
+        n = C.c_int32()
+        check(self.lib.dab_get_point_priors(self.h, C.byref(n), None, None, None, None), self.lib)
+        r = np.zeros((n.value, 3))
+        cost = C.c_double()
+        check(self.lib.dab_eval_point_priors(self.h, _ptr(r, C.c_double), C.byref(cost)), self.lib)
+        return r, cost.value
+
     def get_intrinsics(self):
         """The intrinsics on the handle, [num_intr][6] (refined ones after a solve)."""
         k = np.zeros((int(self.problem.intr.shape[0]), 6))
@@ -597,8 +651,20 @@ def sqrt_info_from_sigmas(sigma_w, sigma_t, n=None):
     return a if n is None else np.repeat(a[None], int(n), axis=0)
 
 
+def point_sqrt_info_from_sigmas(sigma, n=None):
+    """sqrt_info of independent point priors: diag(1 / sigma), sigma a scalar or one value per axis,
+    one 3x3 or [n] of them. np.inf (or None) as a sigma gives a zero row:
+    point_sqrt_info_from_sigmas((np.inf, np.inf, 0.01)) is height-only control."""
+    sg = [sigma] * 3 if sigma is None or np.ndim(sigma) == 0 else list(sigma)
+    if len(sg) != 3:
+        raise ValueError("sigma: a scalar or 3 values")
+    a = np.diag([0.0 if v is None or np.isinf(v) else 1.0 / float(v) for v in sg])
+    return a if n is None else np.repeat(a[None], int(n), axis=0)
+
+
 def solve(problem, max_iteration=1000, max_second=3600, freeze_camera=False, device=0,
-          verbose=False, loss=None, free_intrinsics=0, freeze_points=False, ext_priors=None, **opt_kw):
+          verbose=False, loss=None, free_intrinsics=0, freeze_points=False, ext_priors=None, point_priors=None,
+          **opt_kw):
     """Drop-in for the reference's solve() (src/sfm.cc:31): DENSE_SCHUR-equivalent LM,
     max_num_iterations / max_solver_time_in_seconds as given, parameters updated in place.
     loss: None (the reference's NULL loss, sfm.cc:48) or a (kind, scale) pair such as
@@ -609,7 +675,9 @@ def solve(problem, max_iteration=1000, max_second=3600, freeze_camera=False, dev
     `SetParameterBlockConstant(parameter_block[0]); //freeze point3d` the reference keeps
     commented out at sfm.cc:59 (pose-only refinement, ground-control points).
     ext_priors: None or (index, mean, sqrt_info), Gaussian priors on extrinsics
-    (Solver.set_ext_priors; sqrt_info_from_sigmas builds the diagonal case)."""
+    (Solver.set_ext_priors; sqrt_info_from_sigmas builds the diagonal case).
+    point_priors: None or (index, mean, sqrt_info), Gaussian priors on points, applied after
+    freeze_points (Solver.set_point_priors; point_sqrt_info_from_sigmas builds the diagonal case)."""
     problem.freeze_camera = bool(freeze_camera)
     o = options(max_num_iterations=max_iteration, max_solver_time_in_seconds=float(max_second),
                 minimizer_progress_to_stdout=int(verbose), **opt_kw)
@@ -624,6 +692,8 @@ def solve(problem, max_iteration=1000, max_second=3600, freeze_camera=False, dev
             s.set_points_constant(freeze_points)
         if ext_priors is not None:
             s.set_ext_priors(*ext_priors)
+        if point_priors is not None:
+            s.set_point_priors(*point_priors)
         return s.solve(o)
     finally:
         s.close()

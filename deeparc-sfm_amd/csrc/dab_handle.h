@@ -163,6 +163,9 @@ enum Slot {
   S_CFX = 16,  // two sets of kFxWords, alternating between passes
   S_XERR = S_CFX + 2 * kFxWords,  // k_eval_bal's error word (uint32 bits; 0 = ok)
   S_PRIOR,  // 0.5 sum |A (x - mu)|^2 over the effective extrinsic priors at x (k_prior_blocks)
+  S_PPRIOR,  // the same over this rank's effective point priors (k_pt_prior_blocks), then over the ranks
+  S_SYNC,    // 2 words: what a multi-rank call decides once for all ranks (call_state), max-reduced
+  S_SYNC1,
   S_NSLOTS
 };
 
@@ -371,6 +374,20 @@ struct Handle {
   std::vector<double> prior_A;            // [count][6][6] row-major
   bool prior_dirty = false;               // lz.d_prior_* do not hold the effective set
   int n_prior = 0;                        // effective priors (of the last sync)
+  // point priors (dab_set_point_priors), as set: state of the handle, reset by dab_set_problem.
+  // pt_prior_sync (after pt_const_sync) works out this rank's effective set (the point is
+  // referenced here and not constant), sorted by device point, at each call that honours it;
+  // call_state then tells whether any rank has one (pt_prior_any: the calls are collective, every
+  // rank takes the same path). n_pt_prior = 0 and pt_prior_any = false while no rank has one, and
+  // no kernel runs then.
+  std::vector<int> pt_prior_idx;          // [count] caller's point ids
+  std::vector<double> pt_prior_mean;      // [count][3]
+  std::vector<double> pt_prior_A;         // [count][3][3] row-major
+  bool pt_prior_dirty = false;            // lz.d_ptp_* do not hold the effective set
+  std::vector<int> pt_prior_pos;          // [count] place in the effective set or -1 (of the last upload)
+  int pt_prior_n = 0;                     // size of the effective set (of the last upload)
+  int n_pt_prior = 0;                     // effective point priors of this rank (of the last sync)
+  bool pt_prior_any = false;              // some rank has an effective point prior (of the last sync)
   int ldz = 0;
   // Buffers allocated from `dev` by the first call that needs them (null / capacity 0: not yet).
   // They die with dev.release(): dab_set_problem resets this whole sub-object there, so a member
@@ -396,6 +413,13 @@ struct Handle {
     double* d_prior_part = nullptr;  // [2 n] per-prior terms of k_prior_blocks / k_prior_candidate
     unsigned* d_prior_cnt = nullptr; // their arrival count (zero between launches)
     int prior_cap = 0;
+    // effective point priors (pt_prior_sync): device point and the planar records [kPtPriorRec][n]
+    int* d_ptp_idx = nullptr;
+    double* d_ptp_rec = nullptr;
+    double* d_ptp_res = nullptr;   // [n][3] + cost: dab_eval_point_priors
+    double* d_ptp_part = nullptr;  // [2 groups] work-group sums of k_pt_prior_blocks / k_pt_prior_candidate
+    unsigned* d_ptp_cnt = nullptr; // their arrival count (zero between launches), apart from d_prior_cnt
+    int ptp_cap = 0;
     size_t bpart_cap = 0, Sz_cap = 0;
     // dab_covariance: Z = L^-1 [n][lds], the point blocks [NP][6], the extrinsic blocks [NC][21],
     // the rank test's scalars and partials
@@ -672,6 +696,18 @@ int pt_const_sync(dab_handle* h);
 int prior_sync(dab_handle* h);
 // 0.5 sum |r|^2 of the effective priors as the last evaluation left it in h_scal (0 without any)
 inline double prior_cost(const Handle* h) { return h->n_prior > 0 ? h->h_scal[S_PRIOR] : 0.0; }
+
+// ---- dab_problem.hip: point priors ----
+// this rank's effective set of the point priors on the handle -> lz.d_ptp_* / h->n_pt_prior
+// (uploaded when changed; no collective). After pt_const_sync.
+int pt_prior_sync(dab_handle* h);
+// What a call decides once for all ranks, after pt_const_sync and pt_prior_sync, with one
+// max-reduce of two words on a multi-rank handle (none on one rank): *points_state = 2 when some
+// rank has a free referenced point, 1 when none has and some rank has a constant one, 0 without
+// referenced points; h->pt_prior_any = some rank has an effective point prior.
+int call_state(dab_handle* h, int* points_state);
+// 0.5 sum |r|^2 of the effective point priors of all ranks as the last evaluation left it in h_scal
+inline double pt_prior_cost(const Handle* h) { return h->pt_prior_any ? h->h_scal[S_PPRIOR] : 0.0; }
 
 // ---- dab_schur_tables.hip: tables and buffers of the linear solvers, built on first use ----
 int build_schur_tables(dab_handle* h);

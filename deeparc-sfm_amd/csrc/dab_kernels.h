@@ -347,6 +347,28 @@ void launch_prior_candidate(hipStream_t s, int n, const int2* idx, const double*
 // res[i][6] = r of prior i, res[6 n] = 0.5 sum |r|^2 in prior order
 void launch_prior_eval(hipStream_t s, int n, const int2* idx, const double* rec, const double* ext, double* res);
 
+// ---- point priors (dab_set_point_priors; dab_k_ptprior.hip) ----------------------------------
+// The n effective priors of this rank, sorted by device point: idx[i] = device point and the
+// planar records rec[kPtPriorRec][n] = mean (3) | A row-major (9) | A^T A packed as V packs it (6).
+// r = A (X - mean), X = points[idx[i]]. One lane per prior, kPtPriorBlock per work-group; every
+// V | g slot has one owner lane and every sum a fixed order (no floating-point atomics). Launched
+// only for n > 0, on the rank that owns the points. part[2 pt_prior_groups(n)]: work-group sums,
+// added by the last work-group to arrive; *cnt: its arrival count, zero between launches.
+constexpr int kPtPriorRec = 18;
+constexpr int kPtPriorBlock = 256;
+inline int pt_prior_groups(int n) { return (n + kPtPriorBlock - 1) / kPtPriorBlock; }
+// V[k][p] += (A^T A)_k, g[k][p] += (A^T r)_k (V [6][NP], g [3][NP]); *cost = 0.5 sum |r|^2
+void launch_pt_prior_blocks(hipStream_t s, int n, int NP, const int* idx, const double* rec, const double* points,
+                            double* V, double* g, double* part, unsigned* cnt, double* cost);
+// model[0] += -sum m.(r + m/2), m = A delta_p; model[1] += sum |A (points_c - mean)|^2; model[2] += 1
+// when that sum is not finite (model = this rank's d_scal + S_MODEL, after the candidate pass's
+// final sum and before the sum over the ranks); delta_p [3][NP] is the unscaled point step
+void launch_pt_prior_candidate(hipStream_t s, int n, int NP, const int* idx, const double* rec, const double* points,
+                               const double* points_c, const double* delta_p, double* part, unsigned* cnt,
+                               double* model);
+// res[i][3] = r of effective prior i, res[3 n] = 0.5 sum |r|^2
+void launch_pt_prior_eval(hipStream_t s, int n, const int* idx, const double* rec, const double* points, double* res);
+
 // ---- free intrinsics in the exact Schur step (dab_set_intrinsics_free; dab_k_intr.hip) -----
 // meta[NI]: x = free intrinsic index or -1; y = active columns (bits 0..5: cx cy f0 f1 k0 k1
 // selected by the mask and present in the model) | columns present in the model << 8 |

@@ -1303,6 +1303,7 @@ extern "C" int dab_set_points_constant(dab_handle* h, const uint8_t* mask) {
   if (mask) h->pt_const.assign(mask, mask + n);
   else h->pt_const.clear();
   h->pt_const_dirty = true;
+  h->pt_prior_dirty = true;  // the effective point priors are those on non-constant points
   return 0;
 }
 extern "C" int dab_get_points_constant(dab_handle* h, uint8_t* mask, int32_t* num_constant) {
@@ -1449,6 +1450,171 @@ extern "C" int dab_eval_ext_priors(dab_handle* h, double* residuals, double* cos
   return guard_fail(h, "dab_eval_ext_priors");
 }
 
+// ------------------------------------------------------------------------------------
+// point priors: host state
+// ------------------------------------------------------------------------------------
+// Per prior as set: its device point when it is effective (the point is referenced on this rank
+// and not constant), else -1.
+static void pt_prior_device_points(const dab_handle* h, std::vector<int>* dev) {
+  dev->assign(h->pt_prior_idx.size(), -1);
+  if (h->pt_prior_idx.empty() || h->NP <= 0) return;
+  std::vector<int> local((size_t)h->prob.num_points, -1);
+  for (int l = 0; l < h->NP; ++l) local[(size_t)h->pt_of[(size_t)l]] = l;
+  for (size_t i = 0; i < h->pt_prior_idx.size(); ++i) {
+    const size_t p = (size_t)h->pt_prior_idx[i];
+    if (local[p] >= 0 && (h->pt_const.empty() || h->pt_const[p] == 0)) (*dev)[i] = local[p];
+  }
+}
+// This rank's effective set in device point order, as device records for the calls that honour
+// it: idx and the planar records [kPtPriorRec][n], A^T A formed once here, uploaded only when the
+// priors, the constant mask or the problem changed. Empty: n_pt_prior stays 0 and nothing touches
+// the device.
+int dab::pt_prior_sync(dab_handle* h) {
+  h->n_pt_prior = 0;
+  if (h->pt_prior_idx.empty() || h->NP <= 0) return 0;
+  if (h->pt_prior_dirty) {
+    std::vector<int> dev;
+    pt_prior_device_points(h, &dev);
+    std::vector<std::pair<int, int>> order;  // (device point, prior as set)
+    for (size_t i = 0; i < dev.size(); ++i)
+      if (dev[i] >= 0) order.emplace_back(dev[i], (int)i);
+    std::sort(order.begin(), order.end());
+    const int n = (int)order.size();
+    h->pt_prior_pos.assign(dev.size(), -1);
+    for (int j = 0; j < n; ++j) h->pt_prior_pos[(size_t)order[(size_t)j].second] = j;
+    if (n > h->lz.ptp_cap) {
+      h->dev.drop(h->lz.d_ptp_idx);
+      h->dev.drop(h->lz.d_ptp_rec);
+      h->dev.drop(h->lz.d_ptp_res);
+      h->dev.drop(h->lz.d_ptp_part);
+      h->lz.d_ptp_idx = nullptr;
+      h->lz.d_ptp_rec = h->lz.d_ptp_res = h->lz.d_ptp_part = nullptr;
+      h->lz.ptp_cap = 0;
+      CHECK_RC(h->dev.alloc(&h->lz.d_ptp_idx, (size_t)n));
+      CHECK_RC(h->dev.alloc(&h->lz.d_ptp_rec, (size_t)kPtPriorRec * n));
+      CHECK_RC(h->dev.alloc(&h->lz.d_ptp_res, (size_t)3 * n + 1));
+      CHECK_RC(h->dev.alloc(&h->lz.d_ptp_part, (size_t)2 * pt_prior_groups(n)));
+      if (!h->lz.d_ptp_cnt) CHECK_RC(h->dev.alloc(&h->lz.d_ptp_cnt, (size_t)2));
+      h->lz.ptp_cap = n;
+    }
+    if (n > 0) {
+      std::vector<int> idx((size_t)n);
+      std::vector<double> rec((size_t)kPtPriorRec * n);
+      const size_t ns = (size_t)n;
+      for (size_t j = 0; j < ns; ++j) {
+        idx[j] = order[j].first;
+        const size_t i = (size_t)order[j].second;
+        const double* A = h->pt_prior_A.data() + 9 * i;
+        for (int k = 0; k < 3; ++k) rec[k * ns + j] = h->pt_prior_mean[3 * i + k];
+        for (int k = 0; k < 9; ++k) rec[(3 + k) * ns + j] = A[k];
+        int q = 12;  // (0,0) (0,1) (0,2) (1,1) (1,2) (2,2), as V
+        for (int a = 0; a < 3; ++a)
+          for (int b = a; b < 3; ++b) {
+            double t = 0.0;
+            for (int r = 0; r < 3; ++r) t += A[3 * r + a] * A[3 * r + b];
+            rec[(size_t)(q++) * ns + j] = t;
+          }
+      }
+      HIP_OK(hipMemcpyAsync(h->lz.d_ptp_idx, idx.data(), sizeof(int) * ns, hipMemcpyHostToDevice, h->stream));
+      HIP_OK(hipMemcpyAsync(h->lz.d_ptp_rec, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice,
+                            h->stream));
+      HIP_OK(hipStreamSynchronize(h->stream));  // idx, rec go out of scope
+    }
+    h->pt_prior_n = n;
+    h->pt_prior_dirty = false;
+  }
+  if (h->pt_prior_n == 0) return 0;
+  // the arrival count starts every call that launches the point-prior kernels at zero
+  HIP_OK(hipMemsetAsync(h->lz.d_ptp_cnt, 0, sizeof(unsigned) * 2, h->stream));
+  h->n_pt_prior = h->pt_prior_n;
+  return 0;
+}
+int dab::call_state(dab_handle* h, int* points_state) {
+  double st[2] = {h->NP - h->n_pt_const > 0 ? 2.0 : (h->n_pt_const > 0 ? 1.0 : 0.0), h->n_pt_prior > 0 ? 1.0 : 0.0};
+  if (h->coll()) {
+    hipStream_t s = h->stream;
+    h->h_scal[S_SYNC] = st[0];
+    h->h_scal[S_SYNC1] = st[1];
+    HIP_OK(hipMemcpyAsync(h->d_scal + S_SYNC, &h->h_scal[S_SYNC], 2 * sizeof(double), hipMemcpyHostToDevice, s));
+    CHECK_RC(h->allreduce(h->d_scal + S_SYNC, 2, ncclMax));
+    HIP_OK(hipMemcpyAsync(&h->h_scal[S_SYNC], h->d_scal + S_SYNC, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    st[0] = h->h_scal[S_SYNC];
+    st[1] = h->h_scal[S_SYNC1];
+  }
+  if (points_state) *points_state = (int)st[0];
+  h->pt_prior_any = st[1] > 0.0;
+  return 0;
+}
+extern "C" int dab_set_point_priors(dab_handle* h, int32_t count, const int32_t* point_index, const double* mean,
+                                    const double* sqrt_info) {
+  clear_error();
+  if (!h) return set_error(DAB_E_INVALID, "null handle");
+  if (!h->have_problem) return set_error(DAB_E_STATE, "no problem set");
+  if (count < 0) return set_error(DAB_E_INVALID, "negative prior count");
+  if (count > 0 && (!point_index || !mean || !sqrt_info)) return set_error(DAB_E_INVALID, "null prior array");
+  const int npts = h->prob.num_points;
+  std::vector<uint8_t> seen((size_t)std::max(1, npts), 0);
+  for (int i = 0; i < count; ++i) {
+    const int p = point_index[i];
+    if (p < 0 || p >= npts) return set_error(DAB_E_INVALID, "prior on a point index out of range");
+    if (seen[(size_t)p]) return set_error(DAB_E_INVALID, "two priors on one point");
+    seen[(size_t)p] = 1;
+  }
+  for (size_t i = 0; i < (size_t)3 * count; ++i)
+    if (!std::isfinite(mean[i])) return set_error(DAB_E_INVALID, "prior mean is not finite");
+  for (size_t i = 0; i < (size_t)9 * count; ++i)
+    if (!std::isfinite(sqrt_info[i])) return set_error(DAB_E_INVALID, "prior sqrt_info is not finite");
+  h->pt_prior_idx.assign(point_index, point_index + count);
+  h->pt_prior_mean.assign(mean, mean + (size_t)3 * count);
+  h->pt_prior_A.assign(sqrt_info, sqrt_info + (size_t)9 * count);
+  h->pt_prior_dirty = true;
+  h->n_pt_prior = 0;
+  h->pt_prior_any = false;
+  return 0;
+}
+extern "C" int dab_get_point_priors(dab_handle* h, int32_t* count, int32_t* num_effective, int32_t* point_index,
+                                    double* mean, double* sqrt_info) {
+  clear_error();
+  if (!h) return set_error(DAB_E_INVALID, "null handle");
+  if (!h->have_problem) return set_error(DAB_E_STATE, "no problem set");
+  if (count) *count = (int32_t)h->pt_prior_idx.size();
+  if (num_effective) {
+    std::vector<int> dev;
+    pt_prior_device_points(h, &dev);
+    int c = 0;
+    for (int d : dev) c += d >= 0;
+    *num_effective = c;
+  }
+  if (point_index) std::copy(h->pt_prior_idx.begin(), h->pt_prior_idx.end(), point_index);
+  if (mean) std::copy(h->pt_prior_mean.begin(), h->pt_prior_mean.end(), mean);
+  if (sqrt_info) std::copy(h->pt_prior_A.begin(), h->pt_prior_A.end(), sqrt_info);
+  return 0;
+}
+extern "C" int dab_eval_point_priors(dab_handle* h, double* residuals, double* cost) {
+  clear_error();
+  if (!h) return set_error(DAB_E_INVALID, "null handle");
+  if (!h->have_problem) return set_error(DAB_E_STATE, "no problem set");
+  HIP_OK(hipSetDevice(h->device));
+  CHECK_RC(pt_prior_sync(h));  // this rank's: the call is not collective
+  const int n = h->n_pt_prior;
+  std::vector<double> res((size_t)3 * n + 1, 0.0);
+  if (n > 0) {
+    launch_pt_prior_eval(h->stream, n, h->lz.d_ptp_idx, h->lz.d_ptp_rec, h->d_points, h->lz.d_ptp_res);
+    HIP_OK(hipMemcpyAsync(res.data(), h->lz.d_ptp_res, sizeof(double) * res.size(), hipMemcpyDeviceToHost,
+                          h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));
+  }
+  if (residuals) {  // as set: an ignored prior's row is zero
+    for (size_t i = 0; i < h->pt_prior_idx.size(); ++i) {
+      const int j = n > 0 ? h->pt_prior_pos[i] : -1;
+      for (int k = 0; k < 3; ++k) residuals[3 * i + k] = j >= 0 ? res[(size_t)3 * j + k] : 0.0;
+    }
+  }
+  if (cost) *cost = res[(size_t)3 * n];
+  return guard_fail(h, "dab_eval_point_priors");
+}
+
 extern "C" int dab_set_problem(dab_handle* h, const dab_problem* p) {
   const int rc = set_problem_impl(h, p);
   CHECK_RC(guard_fail(h, "dab_set_problem"));
@@ -1477,6 +1643,13 @@ static int set_problem_impl(dab_handle* h, const dab_problem* p) {
   h->prior_A.clear();
   h->prior_dirty = true;
   h->n_prior = 0;
+  h->pt_prior_idx.clear();  // no point priors (num_points may have changed)
+  h->pt_prior_mean.clear();
+  h->pt_prior_A.clear();
+  h->pt_prior_pos.clear();
+  h->pt_prior_dirty = true;
+  h->pt_prior_n = h->n_pt_prior = 0;
+  h->pt_prior_any = false;
   PhaseTimer phase{"set_problem %-22s %8.1f ms\n"};  // the host preprocessing's phases
   const int N = p->num_obs;
   h->N = N;

@@ -244,6 +244,14 @@ int dab::eval_jacobian_and_blocks(dab_handle* h, bool with_norms, bool tables_cu
   // overlapped one too) and before the norms, the Jacobi scale and every step kernel read them
   launch_prior_blocks(s, h->n_prior, h->lz.d_prior_idx, h->lz.d_prior_rec, h->d_ext, h->ug(), h->lz.d_prior_part,
                       h->lz.d_prior_cnt, h->d_scal + S_PRIOR);
+  // point priors: A^T A | A^T r into this rank's V | g (a point belongs to one rank), before the
+  // point gradient's norms, the Jacobi scale and the point factor read them. A rank without any,
+  // where another has one, leaves a zero for the sum over the ranks
+  if (h->n_pt_prior > 0)
+    launch_pt_prior_blocks(s, h->n_pt_prior, h->NP, h->lz.d_ptp_idx, h->lz.d_ptp_rec, h->d_points, h->d_V, h->d_g,
+                           h->lz.d_ptp_part, h->lz.d_ptp_cnt, h->d_scal + S_PPRIOR);
+  else if (h->pt_prior_any)
+    HIP_OK(hipMemsetAsync(h->d_scal + S_PPRIOR, 0, sizeof(double), s));
   if (with_norms) {
     launch_grad_points_m(s, h->NP, h->d_points, h->d_g, h->d_gpart, h->red_grid, h->d_ptc);
     launch_final_sum(s, h->red_grid, 3, h->d_gpart, h->d_scal + S_GMAX_P, 1u);
@@ -252,6 +260,7 @@ int dab::eval_jacobian_and_blocks(dab_handle* h, bool with_norms, bool tables_cu
   }
   // cross-rank: sums of cost, bad, gnorm, xnorm; max of gmax
   CHECK_RC(h->allreduce_cost());
+  if (h->pt_prior_any) CHECK_RC(h->allreduce(h->d_scal + S_PPRIOR, 1, ncclSum));
   if (with_norms) {
     CHECK_RC(h->allreduce(h->d_scal + S_GMAX_P, 1, ncclMax));
     CHECK_RC(h->allreduce(h->d_scal + S_GNORM_P, 2, ncclSum));
@@ -338,24 +347,6 @@ static double elapsed_collective(dab_handle* h, double local) {
     return -1.0;
   if (hipStreamSynchronize(s) != hipSuccess) return -1.0;
   return h->h_scal[S_TIME];
-}
-
-// Constant points, decided once per solve for all ranks with one max-reduce: 2 when some rank has
-// a free referenced point, 1 when none has and some rank has a constant one (no free point in the
-// problem), 0 when there are no referenced points at all. Expects pt_const_sync's counts.
-static int points_state(dab_handle* h, int* state) {
-  double local = h->NP - h->n_pt_const > 0 ? 2.0 : (h->n_pt_const > 0 ? 1.0 : 0.0);
-  if (h->coll()) {
-    hipStream_t s = h->stream;
-    h->h_scal[S_TIME] = local;
-    HIP_OK(hipMemcpyAsync(h->d_scal + S_TIME, &h->h_scal[S_TIME], sizeof(double), hipMemcpyHostToDevice, s));
-    CHECK_RC(h->allreduce(h->d_scal + S_TIME, 1, ncclMax));
-    HIP_OK(hipMemcpyAsync(&h->h_scal[S_TIME], h->d_scal + S_TIME, sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-    local = h->h_scal[S_TIME];
-  }
-  *state = (int)local;
-  return 0;
 }
 
 // ------------------------------------------------------------------------------------
@@ -469,7 +460,8 @@ int dab::cam_system_buffers(dab_handle* h, bool factor, CamSystem* cs) {
   return 0;
 }
 // S of one step (NC > 0): its leading n x n part and the rhs row n, summed over the ranks; the
-// border rows of the block z come after it. x_cost scales the tile path's fixed-point rhs.
+// border rows of the block z come after it. x_cost scales the tile path's fixed-point rhs: the
+// cost of everything that enters q_p, the observations and the point priors of all ranks.
 // with_pm: the point-major Y planes too (the back substitution of dab_solve's pair-table path
 // reads them). The Y records are fp64 and go to d_Yrec: fp32 records exist only in the PCG.
 int dab::cam_system_assemble(dab_handle* h, const CamSystem& cs, const StepScalars& sc, double x_cost, bool with_pm) {
@@ -482,7 +474,7 @@ int dab::cam_system_assemble(dab_handle* h, const CamSystem& cs, const StepScala
     a.kq = 0;
     if (x_cost > 0.0 && std::isfinite(x_cost)) {
       int e2;
-      (void)std::frexp(2.0 * x_cost, &e2);  // sum_p |q_p|^2 <= 2 cost < 2^e2
+      (void)std::frexp(2.0 * x_cost, &e2);  // sum_p |q_p|^2 <= 2 cost (observations + point priors) < 2^e2
       a.kq = (e2 + 1) >> 1;
     }
     launch_schur_scale(s, NC, h->ug(), h->d_scale_c, h->d_kx);
@@ -537,8 +529,10 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
   // constant points: this rank's set, and whether any rank has a free point left
   CHECK_RC(pt_const_sync(h));
   CHECK_RC(prior_sync(h));  // the effective extrinsic priors (none: no prior kernel is launched)
+  CHECK_RC(pt_prior_sync(h));  // this rank's effective point priors, after pt_const_sync (likewise)
+  // whether any rank has a free point left, and whether any has an effective point prior
   int pstate = 2;
-  CHECK_RC(points_state(h, &pstate));
+  CHECK_RC(call_state(h, &pstate));
   const bool no_free_points = pstate == 1;
   if (opt.linear_solver_type == DAB_LINEAR_SOLVER_AUTO)  // the same choice on every rank (NC is the union's)
     opt.linear_solver_type = h->world <= 1 || h->NC == 0 || mf_schur_fits(h->NC, h->E, h->NI) ||
@@ -595,7 +589,7 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
   sum->iterations_written = 0;
   sum->num_successful_steps = sum->num_unsuccessful_steps = 0;
   sum->num_iterations = 0;
-  sum->num_residuals = 2 * h->N + 6 * h->n_prior;
+  sum->num_residuals = 2 * h->N + 6 * h->n_prior + 3 * h->n_pt_prior;  // this rank's, as 2 N is
   sum->num_parameters = 3 * (NP - h->n_pt_const) + 6 * NC + cs.nz_scal;
   sum->num_free_points = NP - h->n_pt_const;
   sum->num_free_ext = NC;
@@ -638,10 +632,18 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
   if (timing) std::fprintf(stderr, "solve iteration 0: %.2f ms\n", 1e3 * (now_s() - t0));
   launch_jacobi_scale(h, nfi, opt.jacobi_scaling);
   sum->jacobian_evaluation_time_in_seconds += now_s() - t0;
-  // x_obs: the observations' part, which bounds the tile assembly's fixed-point rhs
-  double x_obs = 0.5 * h->h_scal[S_COST];
-  double x_cost = h->n_prior > 0 ? x_obs + prior_cost(h) : x_obs;
-  bool eval_ok = h->h_scal[S_COST_BAD] == 0.0 && std::isfinite(prior_cost(h));
+  // x_rhs: the observations' cost and the point priors' (all ranks): both enter q_p, so together
+  // they bound the tile assembly's fixed-point rhs. The extrinsic priors' part never enters q_p
+  // and stays out of that bound (it could only loosen it).
+  auto cost_at_x = [&](double* rhs) {
+    const double obs = 0.5 * h->h_scal[S_COST];
+    *rhs = h->pt_prior_any ? obs + pt_prior_cost(h) : obs;
+    const double c = h->n_prior > 0 ? obs + prior_cost(h) : obs;
+    return h->pt_prior_any ? c + pt_prior_cost(h) : c;
+  };
+  double x_rhs;
+  double x_cost = cost_at_x(&x_rhs);
+  bool eval_ok = h->h_scal[S_COST_BAD] == 0.0 && std::isfinite(prior_cost(h)) && std::isfinite(pt_prior_cost(h));
   double gmax = std::max(h->h_scal[S_GMAX_P], h->h_scal[S_CAM0 + 2]);
   double x_norm = std::sqrt(h->h_scal[S_XNORM_P] + h->h_scal[S_CAM0 + 4]);
   if (nfi > 0) {
@@ -742,7 +744,7 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
       it.linear_solver_iterations = cg_iters;
       pcg_fail = cg_status == kPcgFailure;
     } else if (NC > 0) {
-      CHECK_RC(cam_system_assemble(h, cs, sc, x_obs, true));
+      CHECK_RC(cam_system_assemble(h, cs, sc, x_rhs, true));
       CHECK_RC(intr_border_rows(h, nfi, sc, cs.S, cs.ld));
       if (chol_factor_solve(h->chol, s, n2, cs.S, cs.ld, yc_, h->d_flags + 1) != 0)
         return set_error(DAB_E_DEVICE, "dense Cholesky launch failed");
@@ -773,6 +775,10 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
       launch_candidate(s, v, h->d_points, h->d_camtab, h->d_dp, h->d_dc, h->d_camtab_c, h->d_gpart, h->red_grid);
     }
     launch_final_sum(s, h->red_grid, 3, h->d_gpart, h->d_scal + S_MODEL);
+    // the point priors' part of the model cost change and of the candidate's cost: this rank's,
+    // after the final sum that writes those slots (same stream) and before the sum over the ranks
+    launch_pt_prior_candidate(s, h->n_pt_prior, NP, h->lz.d_ptp_idx, h->lz.d_ptp_rec, h->d_points, h->d_points_c,
+                              h->d_dp, h->lz.d_ptp_part, h->lz.d_ptp_cnt, h->d_scal + S_MODEL);
     CHECK_RC(h->allreduce(h->d_scal + S_MODEL, 5, ncclSum));
     // the priors' part of the model cost change and of the candidate's cost, once, after the sum
     launch_prior_candidate(s, h->n_prior, h->lz.d_prior_idx, h->lz.d_prior_rec, h->d_ext, h->d_ext_c, h->d_dc,
@@ -847,13 +853,12 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
       CHECK_RC(read_znorm());
       CHECK_RC(read_scalars(h));
       sum->jacobian_evaluation_time_in_seconds += now_s() - tj;
-      if (h->h_scal[S_COST_BAD] != 0.0 || !std::isfinite(prior_cost(h))) {
+      if (h->h_scal[S_COST_BAD] != 0.0 || !std::isfinite(prior_cost(h)) || !std::isfinite(pt_prior_cost(h))) {
         term = DAB_FAILURE;
         std::snprintf(sum->message, sizeof(sum->message), "Residual and Jacobian evaluation failed.");
         break;
       }
-      x_obs = 0.5 * h->h_scal[S_COST];
-      x_cost = h->n_prior > 0 ? x_obs + prior_cost(h) : x_obs;
+      x_cost = cost_at_x(&x_rhs);
       gmax = std::max(h->h_scal[S_GMAX_P], h->h_scal[S_CAM0 + 2]);
       if (nfi > 0) gmax = std::max(gmax, hz[8 + 2]);
       it.step_is_successful = 1;

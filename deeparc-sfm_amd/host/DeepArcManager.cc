@@ -357,6 +357,10 @@ void DeepArcManager::clear() {
   extrinsics_.clear();
   camera_.clear();
   hemisphere_.clear();
+  // the point priors index the point list that just went
+  pt_prior_index_.clear();
+  pt_prior_mean_.clear();
+  pt_prior_sqrt_info_.clear();
 }
 
 bool DeepArcManager::read(std::string filename) {
@@ -649,6 +653,26 @@ void DeepArcManager::filterPoint3d(double error_boundary, double* hemisphere_cen
   }
   const size_t np_old = point3d_.size();
   point3d_.resize(w);
+  // the point priors follow the point list: a survivor's under its new index, a removed point's
+  // dropped (never an old index that now names another point)
+  if (!pt_prior_index_.empty()) {
+    std::vector<int> new_index(np_old, -1);
+    for (size_t i = 0, k = 0; i < np_old; ++i)
+      if (keep_pt[i]) new_index[i] = (int)k++;
+    size_t q = 0;
+    for (size_t i = 0; i < pt_prior_index_.size(); ++i) {
+      const int old = pt_prior_index_[i];
+      if (old < 0 || (size_t)old >= np_old || new_index[(size_t)old] < 0) continue;
+      pt_prior_index_[q] = new_index[(size_t)old];
+      std::copy(pt_prior_mean_.begin() + 3 * i, pt_prior_mean_.begin() + 3 * i + 3, pt_prior_mean_.begin() + 3 * q);
+      std::copy(pt_prior_sqrt_info_.begin() + 9 * i, pt_prior_sqrt_info_.begin() + 9 * i + 9,
+                pt_prior_sqrt_info_.begin() + 9 * q);
+      ++q;
+    }
+    pt_prior_index_.resize(q);
+    pt_prior_mean_.resize(3 * q);
+    pt_prior_sqrt_info_.resize(9 * q);
+  }
   const size_t np_new = w;
   w = 0;
   for (size_t i = 0; i < params_.size(); ++i) {

@@ -87,6 +87,26 @@ class DeepArcManager {
   const std::vector<int>& extrinsicPriorIndex() const { return prior_index_; }
   const std::vector<double>& extrinsicPriorMean() const { return prior_mean_; }
   const std::vector<double>& extrinsicPriorSqrtInfo() const { return prior_sqrt_info_; }
+  // Gaussian priors on points for every later solve() of this manager (dab_set_point_priors in
+  // dab.h; Ceres: problem.AddResidualBlock(new NormalPrior(A, mu), NULL, point)): ground-control
+  // points. index into the manager's current point list (point3ds()), mean [n][3], sqrt_info
+  // [n][3][3] row-major = A of the residual A (X - mean). Empty vectors clear them. Kept across
+  // the pipeline's re-set-ups and applied after every dab_set_problem; checked when the solve
+  // applies them to the handle. filterPoint3d renumbers them with the point list: a surviving
+  // point keeps its prior under its new index, a removed point's prior goes with it. clear() (and
+  // so read() of another scene) drops them: their indices name points of the scene they were set
+  // on. Arrays whose lengths do not match index throw and leave the setting as it was.
+  void setPointPriors(const std::vector<int>& index, const std::vector<double>& mean,
+                      const std::vector<double>& sqrt_info) {
+    if (mean.size() != 3 * index.size() || sqrt_info.size() != 9 * index.size())
+      throw "point priors: mean needs 3 and sqrt_info 9 values per index";
+    pt_prior_index_ = index;
+    pt_prior_mean_ = mean;
+    pt_prior_sqrt_info_ = sqrt_info;
+  }
+  const std::vector<int>& pointPriorIndex() const { return pt_prior_index_; }
+  const std::vector<double>& pointPriorMean() const { return pt_prior_mean_; }
+  const std::vector<double>& pointPriorSqrtInfo() const { return pt_prior_sqrt_info_; }
 
   // Covariance of the current scene at its current parameters (dab_covariance in dab.h: Sigma =
   // (J^T J)^-1 under this manager's loss, no sigma^2 factor; ceres::Covariance). The reference's
@@ -129,6 +149,8 @@ class DeepArcManager {
   bool points_const_ = false;  // all free (sfm.cc:59 commented out)
   std::vector<int> prior_index_;  // extrinsic priors (none)
   std::vector<double> prior_mean_, prior_sqrt_info_;
+  std::vector<int> pt_prior_index_;  // point priors (none), indices into point3d_
+  std::vector<double> pt_prior_mean_, pt_prior_sqrt_info_;
   int arc_size_ = 0, ring_size_ = 0;
   bool share_extrinsic_ = false;
   std::map<int, std::map<int, Camera*> > hemisphere_;

@@ -175,6 +175,33 @@ int dam_set_ext_priors(dam_manager* m, int32_t count, const int32_t* ext_index, 
   });
 }
 
+int dam_set_point_priors(dam_manager* m, int32_t count, const int32_t* point_index, const double* mean,
+                         const double* sqrt_info) {
+  return guarded([&] {
+    if (!m) throw "null manager";
+    if (count < 0) throw "negative prior count";
+    if (count > 0 && (!point_index || !mean || !sqrt_info)) throw "null prior array";
+    const size_t n = (size_t)count;
+    const size_t npts = m->m.point3ds()->size();
+    for (size_t i = 0; i < n; ++i)
+      if (point_index[i] < 0 || (size_t)point_index[i] >= npts) throw "prior on a point index out of range";
+    if (n == 0) m->m.setPointPriors({}, {}, {});
+    else
+      m->m.setPointPriors(std::vector<int>(point_index, point_index + n), std::vector<double>(mean, mean + 3 * n),
+                          std::vector<double>(sqrt_info, sqrt_info + 9 * n));
+  });
+}
+
+int dam_get_point_priors(dam_manager* m, int32_t* count, int32_t* point_index, double* mean, double* sqrt_info) {
+  return guarded([&] {
+    if (!m) throw "null manager";
+    if (count) *count = (int32_t)m->m.pointPriorIndex().size();
+    if (point_index) std::copy(m->m.pointPriorIndex().begin(), m->m.pointPriorIndex().end(), point_index);
+    if (mean) std::copy(m->m.pointPriorMean().begin(), m->m.pointPriorMean().end(), mean);
+    if (sqrt_info) std::copy(m->m.pointPriorSqrtInfo().begin(), m->m.pointPriorSqrtInfo().end(), sqrt_info);
+  });
+}
+
 int dam_covariance(dam_manager* m, const int32_t* extra_const, int32_t n_extra, int32_t freeze_camera,
                    double* point_cov, double* ext_cov, double* ext_full, int32_t* ext_label,
                    dab_covariance_info* info) {

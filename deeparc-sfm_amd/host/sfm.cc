@@ -49,6 +49,14 @@ int solveWith(DeepArcManager& m, const dab_options& options, bool freeze_camera,
                             m.extrinsicPriorSqrtInfo().data());
   }
   if (rc) return rc;
+  // the point priors, or none, in the manager's current point numbering (filterPoint3d keeps it
+  // current): likewise after every (re-)set-up
+  {
+    const std::vector<int32_t> idx(m.pointPriorIndex().begin(), m.pointPriorIndex().end());
+    rc = dab_set_point_priors(dh.h, (int32_t)idx.size(), idx.data(), m.pointPriorMean().data(),
+                              m.pointPriorSqrtInfo().data());
+  }
+  if (rc) return rc;
   const double t0 = dab_now_seconds();
   rc = dab_solve(dh.h, &options, s);
   // (not with free intrinsics: they need the exact step, and PCG's refusal would hide the reason)

@@ -48,6 +48,8 @@ SIGNATURES = {
     "dam_set_intrinsics_free": (C.c_int, [C.c_void_p, C.c_int32]),
     "dam_set_points_constant": (C.c_int, [C.c_void_p, C.c_int32]),
     "dam_set_ext_priors": (C.c_int, [C.c_void_p, C.c_int32, _ip, _dp, _dp]),
+    "dam_set_point_priors": (C.c_int, [C.c_void_p, C.c_int32, _ip, _dp, _dp]),
+    "dam_get_point_priors": (C.c_int, [C.c_void_p, _ip, _ip, _dp, _dp]),
     "dam_covariance": (C.c_int, [C.c_void_p, _ip, C.c_int32, C.c_int32, _dp, _dp, _dp, _ip,
                                  C.POINTER(_abi.DabCovarianceInfo)]),
     "dam_covariance_intrinsics": (C.c_int, [C.c_void_p, _ip, C.c_int32, _dp, _dp, _dp, _dp, _ip, _ip,
@@ -177,6 +179,29 @@ class DeepArcManager:
         if mu.shape != (n, 6) or a.shape != (n, 6, 6):
             raise ValueError(f"mean: ({n}, 6) and sqrt_info: ({n}, 6, 6) values")
         _check(self.lib.dam_set_ext_priors(self.h, n, _p(idx, C.c_int32), _p(mu, C.c_double), _p(a, C.c_double)))
+
+    def set_point_priors(self, index, mean=None, sqrt_info=None):
+        """Gaussian priors on points for every later solve() of this manager
+        (dam_set_point_priors; core.Solver.set_point_priors' arguments, index into points()); None
+        or an empty index clears them. filterPoint3d renumbers them with the point list."""
+        if index is None or np.size(index) == 0:
+            _check(self.lib.dam_set_point_priors(self.h, 0, None, None, None))
+            return
+        idx = np.ascontiguousarray(index, np.int32).reshape(-1)
+        n = idx.shape[0]
+        mu = np.ascontiguousarray(mean, np.float64)
+        a = np.ascontiguousarray(sqrt_info, np.float64)
+        if mu.shape != (n, 3) or a.shape != (n, 3, 3):
+            raise ValueError(f"mean: ({n}, 3) and sqrt_info: ({n}, 3, 3) values")
+        _check(self.lib.dam_set_point_priors(self.h, n, _p(idx, C.c_int32), _p(mu, C.c_double), _p(a, C.c_double)))
+
+    def get_point_priors(self):
+        """(index [n], mean [n][3], sqrt_info [n][3][3]) as the manager holds them now."""
+        n = C.c_int32()
+        _check(self.lib.dam_get_point_priors(self.h, C.byref(n), None, None, None))
+        idx, mu, a = np.zeros(n.value, np.int32), np.zeros((n.value, 3)), np.zeros((n.value, 3, 3))
+        _check(self.lib.dam_get_point_priors(self.h, None, _p(idx, C.c_int32), _p(mu, C.c_double), _p(a, C.c_double)))
+        return idx, mu, a
 
     def covariance(self, extra_const=(), freeze_camera=False, full=False):
         """DeepArcManager::covariance (dam_covariance): the covariance of the current scene at its

@@ -428,6 +428,68 @@ int dab_get_ext_priors(dab_handle* h, int32_t* count, int32_t* num_effective, in
                        double* sqrt_info);
 int dab_eval_ext_priors(dab_handle* h, double* residuals /* [count][6], as set; nullable */, double* cost /* nullable */);
 
+/* ---- Gaussian priors on points -----------------------------------------------------------
+ * "This point is known to within sigma", without holding it constant: a surveyed ground-control
+ * point, a calibration-target corner. What in Ceres is
+ *   problem.AddResidualBlock(new ceres::NormalPrior(A, mu), NULL, point)
+ * on a point's block. A prior adds the residual block r = A (X_p - mu) to the problem, X_p =
+ * points[p], A = sqrt_info 3x3 row-major. Rows of A may be zero: height-only control is
+ * A = [0 0 0; 0 0 0; 0 0 1 / sigma]. The prior adds 0.5 |r|^2 to every cost dab_solve and the
+ * covariance calls report and is never under the handle's robust loss (a NULL loss of its own).
+ * It is the third state of a point between "free" and "constant" (dab_set_points_constant), the
+ * soft remedy for the scale gauge dab_covariance needs (the covariance then carries the control
+ * points' uncertainty instead of claiming it is zero), and the only prior that acts with
+ * freeze_camera, where the points are the free parameters.
+ *
+ * The priors are state of the handle, like the loss, the masks and the extrinsic priors: set
+ * after dab_set_problem, which resets them to none (num_points may change); they survive
+ * dab_update_parameters, dab_set_loss, dab_set_intrinsics_free, dab_set_points_constant and
+ * dab_set_ext_priors and take effect at the next dab_solve, dab_covariance or
+ * dab_covariance_intrinsics. count = 0 (arrays may be NULL) clears them. point_index holds the
+ * caller's point ids; at most one prior per point. In a multi-rank handle each rank sets the
+ * priors of the points of its own shard, as with the constant mask (points are sharded: a prior's
+ * sums go in on its rank, before the sums over the ranks); the calls that honour them are
+ * collective already.
+ *
+ * Effective set. A prior is effective when its point is referenced on this rank and not constant.
+ * Any other prior is ignored entirely: no cost, no residual rows, zeros from
+ * dab_eval_point_priors, the same deliberate simplification as for extrinsic priors (Ceres would
+ * carry the constant cost of such a block). freeze_camera does not disable point priors. Without a
+ * free point on any rank (DAB_SCHUR_DIRECT) the effective set is empty by definition.
+ * *num_effective counts this rank's effective priors; dab_summary.num_residuals and both
+ * covariance infos' num_residuals grow by 3 per effective prior of this rank (they count this
+ * rank's observations too), num_parameters is unchanged. With no effective prior on any rank
+ * (never set, count 0, only constant or unreferenced points named) every call gives bitwise what
+ * it gives on a handle that never set one, and no point-prior kernel is launched. (Whether any
+ * rank has an effective prior is a second word in the max-reduce a multi-rank dab_solve already
+ * makes per call; a multi-rank covariance call makes one such small reduce of its own.)
+ *
+ * Where it enters: A^T A and A^T r are added to the point's V | g after each evaluation pass, so
+ * every linear solver, assembly, pcg_fp32, loss, free-intrinsics, constant-points,
+ * extrinsic-prior and freeze_camera combination that works without point priors works with them
+ * (there are no new DAB_E_UNSUPPORTED cases); the model cost change and the candidate cost get the
+ * priors' terms after the candidate pass, before their sum over the ranks. Every prior sum has a
+ * fixed order: two solves agree bitwise, and the result of a one-rank handle does not depend on
+ * the order the priors were set in.
+ *
+ * dab_get_point_priors returns what was set (arrays nullable, sized by a first call for *count).
+ * dab_eval_point_priors is not collective; it evaluates at the parameters now on the handle:
+ * residuals [count][3] in the order set, cost = 0.5 sum |r|^2 over this rank's effective priors.
+ *
+ * dab_eval_residuals, dab_eval_jacobians, dab_filter, dab_bench_eval_pass, dab_bench_get_blocks,
+ * dab_get_intrinsic_blocks and dab_jacobian_bytes ignore point priors (raw observation
+ * quantities; dab_bench_get_blocks reads V | g where the last evaluation left them: raw after
+ * dab_bench_eval_pass, with A^T A | A^T r added after a dab_solve or covariance call with priors).
+ * Errors, all leaving the state unchanged: DAB_E_INVALID for a null handle (checked before any
+ * device use), count < 0, a null array with count > 0, an index outside [0, num_points), a
+ * duplicate index, or a non-finite entry of mean or sqrt_info; DAB_E_STATE before
+ * dab_set_problem. */
+int dab_set_point_priors(dab_handle* h, int32_t count, const int32_t* point_index /* [count], caller's point ids */,
+                         const double* mean /* [count][3] */, const double* sqrt_info /* [count][3][3] row-major */);
+int dab_get_point_priors(dab_handle* h, int32_t* count, int32_t* num_effective, int32_t* point_index, double* mean,
+                         double* sqrt_info);
+int dab_eval_point_priors(dab_handle* h, double* residuals /* [count][3], as set; nullable */, double* cost /* nullable */);
+
 /* ---- evaluation (parity / filterPoint3d) ---------------------------------------------
  * residuals: [num_obs][2] in the caller's observation order.
  * jacobians: [num_obs][2][15] row-major, columns = [X(3) | w0(3) t0(3) | w1(3) t1(3)]
@@ -494,7 +556,8 @@ int dab_filter(dab_handle* h, double error_boundary, const double center[3], dou
  * (Problem.subset in the Python layer), and fix the scale gauge with one constant point
  * (dab_set_points_constant: a ground-control point) or with one more constant extrinsic
  * (ext_const) beside the reference's arc 0 / camera 0; or, softly, with a position prior on one
- * or a few cameras (dab_set_ext_priors), whose uncertainty the covariance then carries.
+ * or a few cameras (dab_set_ext_priors) or a prior on a few ground-control points
+ * (dab_set_point_priors), whose uncertainty the covariance then carries.
  *
  * Multi-rank handles: every rank calls it. S is all-reduced as in the exact step, every rank
  * inverts its own copy (identical camera arrays) and gets the covariances of its own shard's

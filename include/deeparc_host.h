@@ -75,6 +75,18 @@ int dam_set_points_constant(dam_manager* m, int32_t all);
  * the groups and the point flag; a prior on a constant extrinsic is ignored. */
 int dam_set_ext_priors(dam_manager* m, int32_t count, const int32_t* ext_index, const double* mean,
                        const double* sqrt_info);
+/* Gaussian priors on points for every later solve of this manager (dab_set_point_priors in dab.h;
+ * ground-control points): point_index [count] into the manager's current point list (the order of
+ * dam_get_points), mean [count][3], sqrt_info [count][3][3] row-major = A of the residual
+ * A (X - mean). count = 0 clears them. An index outside the point list, a negative count or a null
+ * array with count > 0 return an error and leave the setting as it was; duplicates and non-finite
+ * entries are refused by the solve that applies them. Re-applied after every re-set of the resident
+ * problem. dam_filter_point3d renumbers them with the point list: a surviving point keeps its prior
+ * under its new index, a removed point's prior is dropped. dam_get_point_priors returns the current
+ * setting (arrays nullable, sized by a first call for *count). */
+int dam_set_point_priors(dam_manager* m, int32_t count, const int32_t* point_index, const double* mean,
+                         const double* sqrt_info);
+int dam_get_point_priors(dam_manager* m, int32_t* count, int32_t* point_index, double* mean, double* sqrt_info);
 /* DeepArcManager::covariance: dab_covariance (dab.h) of the manager's current scene at its
  * current parameters, under the manager's loss. extra_const[n_extra]: extrinsic indices held
  * constant beside the gauge rule's; the reference's rule leaves the rig's global scale free

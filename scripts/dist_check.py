@@ -19,6 +19,11 @@ come back bitwise untouched, and with `all` every rank must report the direct ca
 the same on every rank's handle and on the single handle: a prior added once per rank instead of
 once shows as a cost difference far above --tol (the priors' share of the initial cost is printed
 and must be above 100 --tol). Off by default.
+--pt-priors all sets a full Gaussian prior on every point (dab_set_point_priors): all of them on the
+single handle, on each rank those of the points it owns (Problem.shard_point_priors; every rank must
+get at least one). A cost not summed over the ranks or a candidate term added after the sum shows
+as a cost difference far above --tol (the priors' share of the initial cost is printed and must be
+above 100 --tol). Off by default.
 --expect-auto-refused checks instead that LINEAR_SOLVER_AUTO, where it picks PCG (several ranks, a
 camera system that is not a small one), refuses a non-empty free set on every rank.
 --covariance checks dab_covariance instead: every rank calls it on its shard after the solve, and
@@ -74,6 +79,8 @@ def main():
                     "every rank must take the direct camera step, S = U + D^2, also under AUTO)")
     ap.add_argument("--ext-priors", default="", choices=("", "pose"),
                     help="Gaussian priors on every non-constant extrinsic, the same on every handle")
+    ap.add_argument("--pt-priors", default="", choices=("", "all"),
+                    help="Gaussian priors on every point, split over the ranks with the points")
     ap.add_argument("--expect-auto-refused", action="store_true",
                     help="with --free-intrinsics: a rig whose tables do not fit the small-camera paths (135 "
                     "extrinsics), so AUTO picks PCG on several ranks; every rank's dab_solve must return "
@@ -275,7 +282,18 @@ def main():
             pa = np.stack([np.linalg.qr(rng.standard_normal((6, 6)))[0] @ np.diag(1.0 / sig)
                            @ (np.eye(6) + 0.2 * rng.standard_normal((6, 6))) for _ in pidx])
             priors = (pidx, glob.ext[pidx] + sig * rng.standard_normal((len(pidx), 6)), pa)
+        pt_priors = None
+        if a.pt_priors:
+            # A = Q D (I + 0.2 G), D = diag(1 / (0.1, 0.01, 0.001)); mean = start + 2 sigma o normal
+            rng = np.random.default_rng(11)
+            sig = np.array([0.1, 0.01, 0.001])
+            qidx = np.arange(glob.points.shape[0], dtype=np.int32)
+            qa = np.stack([np.linalg.qr(rng.standard_normal((3, 3)))[0] @ np.diag(1.0 / sig)
+                           @ (np.eye(3) + 0.2 * rng.standard_normal((3, 3))) for _ in qidx])
+            pt_priors = (qidx, glob.points + 2.0 * sig * rng.standard_normal((len(qidx), 3)), qa)
         prior_share = 0.0
+        pt_prior_share = 0.0
+        pt_eff = (0, 0)
         live = []
         if a.live_together:  # every handle of this problem created (and its arena slot taken) up front
             for _ in range(3):
@@ -300,6 +318,9 @@ def main():
                     s1.set_ext_priors(*priors)
                     assert s1.get_ext_priors()[3] == len(priors[0])
                     prior_share = s1.eval_ext_priors()[1]
+                if pt_priors is not None:
+                    s1.set_point_priors(*pt_priors)
+                    pt_prior_share = s1.eval_point_priors()[1]
                 ropts = opts
                 if lst == pkg.DAB_LINEAR_SOLVER_AUTO:
                     # what AUTO must pick on several ranks: the exact step for small camera
@@ -309,6 +330,7 @@ def main():
                     ropts = pkg.options(max_num_iterations=a.iters, linear_solver_type=want)
                 ref = (s1.solve(ropts), g1.points.copy(), g1.ext.copy(), g1.intr.copy())
                 prior_share /= ref[0]["initial_cost"]
+                pt_prior_share /= ref[0]["initial_cost"]
                 s1.close()
             dist.barrier()
             mine = glob.copy().shard(rank, world)
@@ -323,6 +345,9 @@ def main():
                 s.set_points_constant(cmask)  # the shard's points are the ones this rank references
             if priors is not None:
                 s.set_ext_priors(*priors)  # the same priors on every rank (include/dab.h)
+            if pt_priors is not None:
+                s.set_point_priors(*glob.shard_point_priors(pt_priors, rank, world))  # this rank's points' priors
+                pt_eff = (s.get_point_priors()[3], len(pt_priors[0]))
             sched = s.eval_fused()
             p2p = s.comm_p2p()
             summ = s.solve(opts)
@@ -363,6 +388,7 @@ def main():
                     intr_moved=float(np.abs(rk - glob.intr).max()) if rk.size else 0.0,
                     num_parameters=(summ["num_parameters"], rs["num_parameters"]),
                     num_residuals=(summ["num_residuals"], rs["num_residuals"], 2 * glob.num_obs), prior_share=prior_share,
+                    pt_prior_share=pt_prior_share, pt_effective=pt_eff,
                     eval_schedule=sched, p2p=p2p,
                     assembly=(int(asm[0]), -int(asm[1]), rs["schur_assembly"]), const_held=bool(held.item()),
                     solver_used=(summ["linear_solver_type_used"], rs["linear_solver_type_used"]))
@@ -384,6 +410,7 @@ def main():
                or (a.expect_no_p2p and v["p2p"] != 0)
                or not v["const_held"]
                or (a.ext_priors and not (v["prior_share"] > 100 * a.tol and v["num_residuals"][1] > v["num_residuals"][2]))
+               or (a.pt_priors and not (v["pt_prior_share"] > 100 * a.tol and 0 < v["pt_effective"][0] < v["pt_effective"][1]))
                or (a.const_points == "all" and v["solver_used"][0] == pkg.DAB_LINEAR_SOLVER_EXPLICIT_SCHUR
                    and v["assembly"] != (pkg.DAB_SCHUR_DIRECT,) * 3)
                or v["solver_used"][0] != v["solver_used"][1]]
