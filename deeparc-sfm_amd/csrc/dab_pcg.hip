@@ -563,6 +563,9 @@ __global__ __launch_bounds__(kOneWG) void k_pcg_update(int NC, int mode, const d
         for (int a = 0; a < 6; ++a) r[6 * c + a] = bvec[6 * c + a] - o[a];
       }
     }
+    // with cross blocks (L = 16) camera c's r is written by thread 16 c and read below by
+    // thread c: without this barrier the Q-test could sum the r of before the reset
+    __syncthreads();
   }
   double acc = 0.0;
   for (int c = threadIdx.x; c < NC; c += blockDim.x) {
