@@ -169,6 +169,9 @@ SIGNATURES = {
     "dab_set_point_priors": (C.c_int, [C.c_void_p, C.c_int32, _ip, _dp, _dp]),
     "dab_get_point_priors": (C.c_int, [C.c_void_p, _ip, _ip, _ip, _dp, _dp]),
     "dab_eval_point_priors": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "dab_set_intr_priors": (C.c_int, [C.c_void_p, C.c_int32, _ip, _dp, _dp]),
+    "dab_get_intr_priors": (C.c_int, [C.c_void_p, _ip, _ip, _ip, _dp, _dp]),
+    "dab_eval_intr_priors": (C.c_int, [C.c_void_p, _dp, _dp]),
     "dab_get_intrinsics": (C.c_int, [C.c_void_p, _dp]),
     "dab_update_intrinsics": (C.c_int, [C.c_void_p, _dp]),
     "dab_eval_intrinsic_jacobians": (C.c_int, [C.c_void_p, _dp]),

@@ -413,6 +413,48 @@ class Solver:
         check(self.lib.dab_eval_point_priors(self.h, _ptr(r, C.c_double), C.byref(cost)), self.lib)
         return r, cost.value
 
+    def set_intr_priors(self, index, mean=None, sqrt_info=None):
+        """Gaussian priors on intrinsics (dab_set_intr_priors; Ceres' NormalPrior(A, mu) with a NULL
+        loss over the intrinsic's three blocks): index [n] intrinsic indices, mean [n][6] in
+        Problem.intr's slots (cx, cy, f0, f1, k0, k1), sqrt_info [n][6][6] = A of the residual
+        A (x - mean). None or an empty index clears them. Set after set_problem, which resets them;
+        they survive update_parameters, update_intrinsics, set_loss, the masks and the other
+        priors. Slots the model lacks or the mask leaves constant take no part; a prior on an
+        intrinsic outside the free set (set_intrinsics_free) is ignored. On a multi-rank handle
+        every rank sets the same priors."""
+        if index is None or np.size(index) == 0:
+            check(self.lib.dab_set_intr_priors(self.h, 0, None, None, None), self.lib)
+            return
+        idx = np.ascontiguousarray(index, np.int32).reshape(-1)
+        n = idx.shape[0]
+        mu = np.ascontiguousarray(mean, np.float64)
+        a = np.ascontiguousarray(sqrt_info, np.float64)
+        if mu.shape != (n, 6) or a.shape != (n, 6, 6):
+            raise ValueError(f"mean: ({n}, 6) and sqrt_info: ({n}, 6, 6) values")
+        check(self.lib.dab_set_intr_priors(self.h, n, _ptr(idx, C.c_int32), _ptr(mu, C.c_double),
+                                           _ptr(a, C.c_double)), self.lib)
+
+    def get_intr_priors(self):
+        """(index [n], mean [n][6], sqrt_info [n][6][6], num_effective) as set."""
+        n, ne = C.c_int32(), C.c_int32()
+        check(self.lib.dab_get_intr_priors(self.h, C.byref(n), C.byref(ne), None, None, None), self.lib)
+        idx = np.zeros(n.value, np.int32)
+        mu = np.zeros((n.value, 6))
+        a = np.zeros((n.value, 6, 6))
+        check(self.lib.dab_get_intr_priors(self.h, None, None, _ptr(idx, C.c_int32), _ptr(mu, C.c_double),
+                                           _ptr(a, C.c_double)), self.lib)
+        return idx, mu, a, ne.value
+
+    def eval_intr_priors(self):
+        """(residuals [n][6] in the order set, cost = 0.5 sum |r|^2 over the effective priors) at
+        the intrinsics on the handle (dab_eval_intr_priors); an ignored prior's row is zero."""
+        n = C.c_int32()
+        check(self.lib.dab_get_intr_priors(self.h, C.byref(n), None, None, None, None), self.lib)
+        r = np.zeros((n.value, 6))
+        cost = C.c_double()
+        check(self.lib.dab_eval_intr_priors(self.h, _ptr(r, C.c_double), C.byref(cost)), self.lib)
+        return r, cost.value
+
     def get_intrinsics(self):
         """The intrinsics on the handle, [num_intr][6] (refined ones after a solve)."""
         k = np.zeros((int(self.problem.intr.shape[0]), 6))
@@ -664,7 +706,7 @@ def point_sqrt_info_from_sigmas(sigma, n=None):
 
 def solve(problem, max_iteration=1000, max_second=3600, freeze_camera=False, device=0,
           verbose=False, loss=None, free_intrinsics=0, freeze_points=False, ext_priors=None, point_priors=None,
-          **opt_kw):
+          intr_priors=None, **opt_kw):
     """Drop-in for the reference's solve() (src/sfm.cc:31): DENSE_SCHUR-equivalent LM,
     max_num_iterations / max_solver_time_in_seconds as given, parameters updated in place.
     loss: None (the reference's NULL loss, sfm.cc:48) or a (kind, scale) pair such as
@@ -677,7 +719,9 @@ def solve(problem, max_iteration=1000, max_second=3600, freeze_camera=False, dev
     ext_priors: None or (index, mean, sqrt_info), Gaussian priors on extrinsics
     (Solver.set_ext_priors; sqrt_info_from_sigmas builds the diagonal case).
     point_priors: None or (index, mean, sqrt_info), Gaussian priors on points, applied after
-    freeze_points (Solver.set_point_priors; point_sqrt_info_from_sigmas builds the diagonal case)."""
+    freeze_points (Solver.set_point_priors; point_sqrt_info_from_sigmas builds the diagonal case).
+    intr_priors: None or (index, mean, sqrt_info), Gaussian priors on the intrinsics that
+    free_intrinsics frees (Solver.set_intr_priors: a calibration with its covariance)."""
     problem.freeze_camera = bool(freeze_camera)
     o = options(max_num_iterations=max_iteration, max_solver_time_in_seconds=float(max_second),
                 minimizer_progress_to_stdout=int(verbose), **opt_kw)
@@ -694,6 +738,8 @@ def solve(problem, max_iteration=1000, max_second=3600, freeze_camera=False, dev
             s.set_ext_priors(*ext_priors)
         if point_priors is not None:
             s.set_point_priors(*point_priors)
+        if intr_priors is not None:
+            s.set_intr_priors(*intr_priors)
         return s.solve(o)
     finally:
         s.close()

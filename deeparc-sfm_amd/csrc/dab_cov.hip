@@ -600,6 +600,7 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
   CHECK_RC(prior_sync(h));  // extrinsic priors: eval_jacobian_and_blocks folds them into U | g_c
   CHECK_RC(pt_prior_sync(h));  // point priors: ... into V | g, so the point factor and the rank test see them
   CHECK_RC(call_state(h, nullptr));  // whether any rank has one (several ranks: one small max-reduce)
+  CHECK_RC(zprior_sync(h, cs.nfi));  // intrinsic priors: into U_zz | g_z after intr_eval (plain dab_covariance: none)
   const int nfree_pts = h->NP - h->n_pt_const;
   hipStream_t s = h->stream;
   const DevView& v = h->view;
@@ -617,7 +618,7 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
   out.num_free_points = nfree_pts;
   out.first_deficient_point = -1;
   out.schur_assembly = h->schur_tiles ? DAB_SCHUR_TILES : DAB_SCHUR_PAIRS;
-  out.num_residuals = 2 * h->N + 6 * h->n_prior + 3 * h->n_pt_prior;
+  out.num_residuals = 2 * h->N + 6 * h->n_prior + 3 * h->n_pt_prior + 6 * h->n_zprior;
   out.num_parameters = 3 * nfree_pts + 6 * NC + cs.nz_scal;
   out.point_pivot_ratio_min = out.camera_pivot_ratio = std::numeric_limits<double>::quiet_NaN();
   for (hipEvent_t& e : h->cov_ev)
@@ -634,11 +635,14 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
   HIP_OK(hipMemsetAsync(h->d_scal + S_XERR, 0, sizeof(double), s));
   HIP_OK(hipEventRecord(h->cov_ev[0], s));
   CHECK_RC(eval_jacobian_and_blocks(h, false));
-  if (nfi > 0) CHECK_RC(intr_eval(h));
+  if (nfi > 0) {
+    CHECK_RC(intr_eval(h));
+    zprior_blocks(h);  // before the Jacobi scale and the border rows read zg
+  }
   launch_jacobi_scale(h, nfi, opt.jacobi_scaling);
   HIP_OK(hipEventRecord(h->cov_ev[1], s));
   CHECK_RC(read_scalars(h));
-  if (h->h_scal[S_COST_BAD] != 0.0 || !std::isfinite(pt_prior_cost(h)))
+  if (h->h_scal[S_COST_BAD] != 0.0 || !std::isfinite(pt_prior_cost(h)) || !std::isfinite(zprior_cost(h)))
     return set_error(DAB_E_INVALID, "residuals are not finite at the current parameters");
   // x_cost bounds the tile assembly's fixed-point rhs: the observations' cost and the point
   // priors' (all ranks), which both enter q_p; the extrinsic priors' never does
@@ -646,6 +650,7 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
   const double x_cost = h->pt_prior_any ? x_obs + pt_prior_cost(h) : x_obs;
   out.cost = h->n_prior > 0 ? x_obs + prior_cost(h) : x_obs;
   if (h->pt_prior_any) out.cost += pt_prior_cost(h);
+  if (h->n_zprior > 0) out.cost += zprior_cost(h);
 
   // ---- point factor without LM diagonal, and the point-side rank test ----
   dab_options lm;

@@ -166,6 +166,7 @@ enum Slot {
   S_PPRIOR,  // the same over this rank's effective point priors (k_pt_prior_blocks), then over the ranks
   S_SYNC,    // 2 words: what a multi-rank call decides once for all ranks (call_state), max-reduced
   S_SYNC1,
+  S_ZPRIOR,  // 0.5 sum |A (x_i - mu)|^2 over the effective intrinsic priors at x (k_zprior_blocks)
   S_NSLOTS
 };
 
@@ -388,6 +389,18 @@ struct Handle {
   int pt_prior_n = 0;                     // size of the effective set (of the last upload)
   int n_pt_prior = 0;                     // effective point priors of this rank (of the last sync)
   bool pt_prior_any = false;              // some rank has an effective point prior (of the last sync)
+  // intrinsic priors (dab_set_intr_priors), as set: state of the handle, reset by dab_set_problem.
+  // zprior_sync (after the free set of the call is on the handle) works out the effective set (the
+  // intrinsic has a free column), sorted by that column, with the inactive columns of A and entries
+  // of the mean zeroed, and leaves its device records in lz.d_zp_*; n_zprior = 0 while the set is
+  // empty, so that no prior kernel is launched then.
+  std::vector<int> zprior_idx;            // [count]
+  std::vector<double> zprior_mean;        // [count][6]
+  std::vector<double> zprior_A;           // [count][6][6] row-major
+  std::vector<int2> zprior_dev_idx;       // host copies of lz.d_zp_idx / lz.d_zp_rec (uploaded on change)
+  std::vector<double> zprior_dev_rec;
+  std::vector<int> zprior_pos;            // [count] place in the effective set or -1 (of the last sync)
+  int n_zprior = 0;                       // effective intrinsic priors (of the last sync)
   int ldz = 0;
   // Buffers allocated from `dev` by the first call that needs them (null / capacity 0: not yet).
   // They die with dev.release(): dab_set_problem resets this whole sub-object there, so a member
@@ -420,6 +433,10 @@ struct Handle {
     double* d_ptp_part = nullptr;  // [2 groups] work-group sums of k_pt_prior_blocks / k_pt_prior_candidate
     unsigned* d_ptp_cnt = nullptr; // their arrival count (zero between launches), apart from d_prior_cnt
     int ptp_cap = 0;
+    // effective intrinsic priors (zprior_sync): (intrinsic, free column), kPriorRec doubles each
+    int2* d_zp_idx = nullptr;       // [kIntrFreeMax]
+    double* d_zp_rec = nullptr;     // [kIntrFreeMax][kPriorRec]
+    double* d_zp_res = nullptr;     // [kIntrFreeMax][6] + cost: dab_eval_intr_priors
     size_t bpart_cap = 0, Sz_cap = 0;
     // dab_covariance: Z = L^-1 [n][lds], the point blocks [NP][6], the extrinsic blocks [NC][21],
     // the rank test's scalars and partials
@@ -708,6 +725,16 @@ int pt_prior_sync(dab_handle* h);
 int call_state(dab_handle* h, int* points_state);
 // 0.5 sum |r|^2 of the effective point priors of all ranks as the last evaluation left it in h_scal
 inline double pt_prior_cost(const Handle* h) { return h->pt_prior_any ? h->h_scal[S_PPRIOR] : 0.0; }
+
+// ---- dab_problem.hip: intrinsic priors ----
+// the effective set of the priors on the handle for the free set now on it (nfi: its size, after
+// intr_free_set / cam_system_free_set; 0 = none) -> lz.d_zp_* / h->n_zprior (uploaded when changed)
+int zprior_sync(dab_handle* h, int nfi);
+// zg[column] += A^T A | A^T r and S_ZPRIOR, after intr_eval's sum over the ranks (no effective
+// prior: no launch)
+void zprior_blocks(dab_handle* h);
+// 0.5 sum |r|^2 of the effective priors as the last evaluation left it in h_scal (0 without any)
+inline double zprior_cost(const Handle* h) { return h->n_zprior > 0 ? h->h_scal[S_ZPRIOR] : 0.0; }
 
 // ---- dab_schur_tables.hip: tables and buffers of the linear solvers, built on first use ----
 int build_schur_tables(dab_handle* h);

@@ -404,6 +404,24 @@ void launch_candidate_z(hipStream_t s, const DevView& v, const double* points, c
                         const double* delta_p, const double* delta_c, const double* camtab_c, const int2* meta,
                         const double* dz, const double* intr_c, double* partial, int grid);
 
+// ---- intrinsic priors (dab_set_intr_priors; dab_k_zprior.hip) --------------------------------
+// The n <= kIntrFreeMax effective priors, sorted by free-intrinsic column: idx[i] = (intrinsic,
+// free column) and rec[i][kPriorRec] = mean (6) | A row-major (36) | A^T A upper-packed as zg
+// packs U_zz (21), the inactive columns of A and entries of mean zeroed on the host (no mask bits
+// here). r = A (x - mean), x = intr[intrinsic][0..5] in the device layout. One work-group each;
+// every zg slot has one owner lane and every sum runs in record order (no floating-point atomics,
+// no arrival counter). Launched only for n > 0, once per pass on every rank, after the pass's sums
+// over the ranks (intrinsics are replicated: the prior counts once).
+// zg[column] += A^T A | A^T r; *cost = 0.5 sum |r|^2
+void launch_zprior_blocks(hipStream_t s, int n, const int2* idx, const double* rec, const double* intr, double* zg,
+                          double* cost);
+// model[0] += -sum m.(r + m/2), m = A dz[column]; model[1] += sum |A (intr_c - mean)|^2; model[2] += 1
+// when that sum is not finite (model = d_scal + S_MODEL after the candidate pass's all-reduce)
+void launch_zprior_candidate(hipStream_t s, int n, const int2* idx, const double* rec, const double* intr,
+                             const double* intr_c, const double* dz, double* model);
+// res[i][6] = r of effective prior i, res[6 n] = 0.5 sum |r|^2 in record order
+void launch_zprior_eval(hipStream_t s, int n, const int2* idx, const double* rec, const double* intr, double* res);
+
 // ---- implicit-Schur PCG (dab_pcg.hip) -------------------------------------------------------
 enum { kPcgRunning = 0, kPcgSuccess = 1, kPcgNoConvergence = 2, kPcgFailure = 3 };
 struct PcgState {

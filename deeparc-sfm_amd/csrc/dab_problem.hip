@@ -1615,6 +1615,154 @@ extern "C" int dab_eval_point_priors(dab_handle* h, double* residuals, double* c
   return guard_fail(h, "dab_eval_point_priors");
 }
 
+// ------------------------------------------------------------------------------------
+// intrinsic priors: host state
+// ------------------------------------------------------------------------------------
+// The effective set of the priors on the handle for the free set now on it (h->intr_meta, nfi of
+// them: the intrinsic is referenced on some rank, has an active scalar, no freeze_camera), sorted
+// by free column so that the order of setting cannot show, as device records: the inactive columns
+// of A and the inactive entries of the mean are zeroed here, A^T A is formed from the zeroed A.
+// Uploaded only when the records differ from the ones on the device. Empty: n_zprior stays 0 and
+// nothing touches the device.
+int dab::zprior_sync(dab_handle* h, int nfi) {
+  h->n_zprior = 0;
+  h->zprior_pos.assign(h->zprior_idx.size(), -1);
+  if (h->zprior_idx.empty() || nfi <= 0 || nfi > kIntrFreeMax) return 0;
+  std::vector<std::pair<int, int>> order;  // (free column, prior as set)
+  for (size_t i = 0; i < h->zprior_idx.size(); ++i) {
+    const int2 mt = h->intr_meta[(size_t)h->zprior_idx[i]];
+    if (mt.x >= 0) order.emplace_back(mt.x, (int)i);
+  }
+  std::sort(order.begin(), order.end());
+  const int n = (int)order.size();
+  if (n == 0) return 0;
+  std::vector<int2> idx((size_t)n);
+  std::vector<double> rec((size_t)kPriorRec * n, 0.0);
+  for (int j = 0; j < n; ++j) {
+    const size_t i = (size_t)order[(size_t)j].second;
+    const int ii = h->zprior_idx[i];
+    const int act = h->intr_meta[(size_t)ii].y & 63;
+    h->zprior_pos[i] = j;
+    idx[(size_t)j] = make_int2(ii, order[(size_t)j].first);
+    double* R = rec.data() + (size_t)kPriorRec * j;
+    double* A = R + 6;
+    for (int k = 0; k < 6; ++k) {
+      if (!((act >> k) & 1)) continue;
+      R[k] = h->zprior_mean[6 * i + k];
+      for (int r = 0; r < 6; ++r) A[6 * r + k] = h->zprior_A[36 * i + 6 * r + k];
+    }
+    int q = 42;
+    for (int a = 0; a < 6; ++a)
+      for (int b = a; b < 6; ++b) {
+        double t = 0.0;
+        for (int r = 0; r < 6; ++r) t += A[6 * r + a] * A[6 * r + b];
+        R[q++] = t;
+      }
+  }
+  if (!h->lz.d_zp_idx) {
+    CHECK_RC(h->dev.alloc(&h->lz.d_zp_idx, (size_t)kIntrFreeMax));
+    CHECK_RC(h->dev.alloc(&h->lz.d_zp_rec, (size_t)kPriorRec * kIntrFreeMax));
+    CHECK_RC(h->dev.alloc(&h->lz.d_zp_res, (size_t)6 * kIntrFreeMax + 1));
+    h->zprior_dev_idx.clear();
+    h->zprior_dev_rec.clear();
+  }
+  bool same = h->zprior_dev_idx.size() == idx.size() && h->zprior_dev_rec.size() == rec.size() &&
+              std::memcmp(h->zprior_dev_rec.data(), rec.data(), sizeof(double) * rec.size()) == 0;
+  for (size_t j = 0; same && j < idx.size(); ++j)
+    same = idx[j].x == h->zprior_dev_idx[j].x && idx[j].y == h->zprior_dev_idx[j].y;
+  if (!same) {
+    HIP_OK(hipMemcpyAsync(h->lz.d_zp_idx, idx.data(), sizeof(int2) * idx.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_OK(hipMemcpyAsync(h->lz.d_zp_rec, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));  // idx, rec are pageable
+    h->zprior_dev_idx = idx;
+    h->zprior_dev_rec = rec;
+  }
+  h->n_zprior = n;
+  return 0;
+}
+void dab::zprior_blocks(dab_handle* h) {
+  launch_zprior_blocks(h->stream, h->n_zprior, h->lz.d_zp_idx, h->lz.d_zp_rec, h->d_intr, h->lz.d_zg,
+                       h->d_scal + S_ZPRIOR);
+}
+extern "C" int dab_set_intr_priors(dab_handle* h, int32_t count, const int32_t* intr_index, const double* mean,
+                                   const double* sqrt_info) {
+  clear_error();
+  if (!h) return set_error(DAB_E_INVALID, "null handle");
+  if (!h->have_problem) return set_error(DAB_E_STATE, "no problem set");
+  if (count < 0) return set_error(DAB_E_INVALID, "negative prior count");
+  if (count > 0 && (!intr_index || !mean || !sqrt_info)) return set_error(DAB_E_INVALID, "null prior array");
+  std::vector<uint8_t> seen((size_t)std::max(1, h->NI), 0);
+  for (int i = 0; i < count; ++i) {
+    const int k = intr_index[i];
+    if (k < 0 || k >= h->NI) return set_error(DAB_E_INVALID, "prior on an intrinsic index out of range");
+    if (seen[(size_t)k]) return set_error(DAB_E_INVALID, "two priors on one intrinsic");
+    seen[(size_t)k] = 1;
+  }
+  for (size_t i = 0; i < (size_t)6 * count; ++i)
+    if (!std::isfinite(mean[i])) return set_error(DAB_E_INVALID, "prior mean is not finite");
+  for (size_t i = 0; i < (size_t)36 * count; ++i)
+    if (!std::isfinite(sqrt_info[i])) return set_error(DAB_E_INVALID, "prior sqrt_info is not finite");
+  h->zprior_idx.assign(intr_index, intr_index + count);
+  h->zprior_mean.assign(mean, mean + (size_t)6 * count);
+  h->zprior_A.assign(sqrt_info, sqrt_info + (size_t)36 * count);
+  h->zprior_pos.assign((size_t)count, -1);
+  h->n_zprior = 0;
+  return 0;
+}
+extern "C" int dab_get_intr_priors(dab_handle* h, int32_t* count, int32_t* num_effective, int32_t* intr_index,
+                                   double* mean, double* sqrt_info) {
+  clear_error();
+  if (!h) return set_error(DAB_E_INVALID, "null handle");
+  if (!h->have_problem) return set_error(DAB_E_STATE, "no problem set");
+  if (count) *count = (int32_t)h->zprior_idx.size();
+  if (num_effective) {
+    int c = 0;
+    if (h->zprior_idx.empty() || !intr_mask_any(h)) {
+      // no prior, or nothing free (freeze_camera too): empty, no device use
+    } else {
+      if (h->coll() && !h->intr_ref_union) {
+        // several ranks, the referenced union not formed yet: the one collective of this call
+        HIP_OK(hipSetDevice(h->device));
+        CHECK_RC(intr_free_set(h, true, nullptr));
+      }
+      for (int i : h->zprior_idx)
+        c += h->intr_ref[(size_t)i] && (intr_struct_bits(h, i) & intr_group_bits(h->intr_mask[(size_t)i])) != 0;
+    }
+    *num_effective = c;
+  }
+  if (intr_index) std::copy(h->zprior_idx.begin(), h->zprior_idx.end(), intr_index);
+  if (mean) std::copy(h->zprior_mean.begin(), h->zprior_mean.end(), mean);
+  if (sqrt_info) std::copy(h->zprior_A.begin(), h->zprior_A.end(), sqrt_info);
+  return 0;
+}
+extern "C" int dab_eval_intr_priors(dab_handle* h, double* residuals, double* cost) {
+  clear_error();
+  if (!h) return set_error(DAB_E_INVALID, "null handle");
+  if (!h->have_problem) return set_error(DAB_E_STATE, "no problem set");
+  HIP_OK(hipSetDevice(h->device));
+  int nfi = 0;
+  if (!h->zprior_idx.empty() && intr_mask_any(h)) {
+    CHECK_RC(intr_free_set(h, true, &nfi));
+    if (nfi > kIntrFreeMax) return set_error(DAB_E_UNSUPPORTED, "more than 16 free intrinsics");
+  }
+  CHECK_RC(zprior_sync(h, nfi));
+  const int n = h->n_zprior;
+  std::vector<double> res((size_t)6 * n + 1, 0.0);
+  if (n > 0) {
+    launch_zprior_eval(h->stream, n, h->lz.d_zp_idx, h->lz.d_zp_rec, h->d_intr, h->lz.d_zp_res);
+    HIP_OK(hipMemcpyAsync(res.data(), h->lz.d_zp_res, sizeof(double) * res.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));
+  }
+  if (residuals) {  // as set: an ignored prior's row is zero
+    for (size_t i = 0; i < h->zprior_idx.size(); ++i) {
+      const int j = h->zprior_pos[i];
+      for (int k = 0; k < 6; ++k) residuals[6 * i + k] = j >= 0 ? res[(size_t)6 * j + k] : 0.0;
+    }
+  }
+  if (cost) *cost = res[(size_t)6 * n];
+  return guard_fail(h, "dab_eval_intr_priors");
+}
+
 extern "C" int dab_set_problem(dab_handle* h, const dab_problem* p) {
   const int rc = set_problem_impl(h, p);
   CHECK_RC(guard_fail(h, "dab_set_problem"));
@@ -1650,6 +1798,13 @@ static int set_problem_impl(dab_handle* h, const dab_problem* p) {
   h->pt_prior_dirty = true;
   h->pt_prior_n = h->n_pt_prior = 0;
   h->pt_prior_any = false;
+  h->zprior_idx.clear();  // no intrinsic priors (num_intr may have changed)
+  h->zprior_mean.clear();
+  h->zprior_A.clear();
+  h->zprior_pos.clear();
+  h->zprior_dev_idx.clear();  // lz went with the release
+  h->zprior_dev_rec.clear();
+  h->n_zprior = 0;
   PhaseTimer phase{"set_problem %-22s %8.1f ms\n"};  // the host preprocessing's phases
   const int N = p->num_obs;
   h->N = N;

@@ -545,6 +545,7 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
   CamSystem cs;
   CHECK_RC(cam_system_free_set(
       h, use_pcg ? "free intrinsics need the exact step (DAB_LINEAR_SOLVER_EXPLICIT_SCHUR)" : nullptr, &cs));
+  CHECK_RC(zprior_sync(h, cs.nfi));  // the effective intrinsic priors of that free set (none: no prior kernel)
   // no free point on any rank: no Schur complement, the camera system is U + D^2 (block diagonal
   // without cross blocks). Not with free intrinsics, nor for an explicitly requested PCG
   const bool direct = no_free_points && !use_pcg && cs.nfi == 0 && h->NC > 0 && h->knobs.points_direct != 0;
@@ -589,7 +590,7 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
   sum->iterations_written = 0;
   sum->num_successful_steps = sum->num_unsuccessful_steps = 0;
   sum->num_iterations = 0;
-  sum->num_residuals = 2 * h->N + 6 * h->n_prior + 3 * h->n_pt_prior;  // this rank's, as 2 N is
+  sum->num_residuals = 2 * h->N + 6 * h->n_prior + 3 * h->n_pt_prior + 6 * h->n_zprior;  // this rank's, as 2 N is
   sum->num_parameters = 3 * (NP - h->n_pt_const) + 6 * NC + cs.nz_scal;
   sum->num_free_points = NP - h->n_pt_const;
   sum->num_free_ext = NC;
@@ -616,6 +617,9 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
   auto intr_at_x = [&]() -> int {
     if (nfi <= 0) return 0;
     CHECK_RC(intr_eval(h));
+    // intrinsic priors: A^T A | A^T r into zg, after the sum over the ranks and before the norms at
+    // x, the Jacobi scale and the border rows read it
+    zprior_blocks(h);
     launch_intr_candidate(s, h->NI, h->lz.d_intr_meta, h->d_intr, h->lz.d_sz, nullptr, h->lz.d_zg, nullptr, nullptr,
                           h->lz.d_znorm + 8);
     return 0;
@@ -634,16 +638,18 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
   sum->jacobian_evaluation_time_in_seconds += now_s() - t0;
   // x_rhs: the observations' cost and the point priors' (all ranks): both enter q_p, so together
   // they bound the tile assembly's fixed-point rhs. The extrinsic priors' part never enters q_p
-  // and stays out of that bound (it could only loosen it).
+  // and stays out of that bound (it could only loosen it), and so does the intrinsic priors'.
   auto cost_at_x = [&](double* rhs) {
     const double obs = 0.5 * h->h_scal[S_COST];
     *rhs = h->pt_prior_any ? obs + pt_prior_cost(h) : obs;
-    const double c = h->n_prior > 0 ? obs + prior_cost(h) : obs;
-    return h->pt_prior_any ? c + pt_prior_cost(h) : c;
+    double c = h->n_prior > 0 ? obs + prior_cost(h) : obs;
+    if (h->pt_prior_any) c += pt_prior_cost(h);
+    return h->n_zprior > 0 ? c + zprior_cost(h) : c;
   };
   double x_rhs;
   double x_cost = cost_at_x(&x_rhs);
-  bool eval_ok = h->h_scal[S_COST_BAD] == 0.0 && std::isfinite(prior_cost(h)) && std::isfinite(pt_prior_cost(h));
+  bool eval_ok = h->h_scal[S_COST_BAD] == 0.0 && std::isfinite(prior_cost(h)) && std::isfinite(pt_prior_cost(h)) &&
+                 std::isfinite(zprior_cost(h));
   double gmax = std::max(h->h_scal[S_GMAX_P], h->h_scal[S_CAM0 + 2]);
   double x_norm = std::sqrt(h->h_scal[S_XNORM_P] + h->h_scal[S_CAM0 + 4]);
   if (nfi > 0) {
@@ -783,6 +789,8 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
     // the priors' part of the model cost change and of the candidate's cost, once, after the sum
     launch_prior_candidate(s, h->n_prior, h->lz.d_prior_idx, h->lz.d_prior_rec, h->d_ext, h->d_ext_c, h->d_dc,
                            h->lz.d_prior_part, h->lz.d_prior_cnt, h->d_scal + S_MODEL);
+    launch_zprior_candidate(s, h->n_zprior, h->lz.d_zp_idx, h->lz.d_zp_rec, h->d_intr, h->lz.d_intr_c, h->lz.d_dz,
+                            h->d_scal + S_MODEL);
     CHECK_RC(h->allreduce_max_i32(h->d_flags, 4));
     CHECK_RC(read_znorm());
     CHECK_RC(read_scalars(h));
@@ -853,7 +861,8 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
       CHECK_RC(read_znorm());
       CHECK_RC(read_scalars(h));
       sum->jacobian_evaluation_time_in_seconds += now_s() - tj;
-      if (h->h_scal[S_COST_BAD] != 0.0 || !std::isfinite(prior_cost(h)) || !std::isfinite(pt_prior_cost(h))) {
+      if (h->h_scal[S_COST_BAD] != 0.0 || !std::isfinite(prior_cost(h)) || !std::isfinite(pt_prior_cost(h)) ||
+          !std::isfinite(zprior_cost(h))) {
         term = DAB_FAILURE;
         std::snprintf(sum->message, sizeof(sum->message), "Residual and Jacobian evaluation failed.");
         break;

@@ -107,6 +107,26 @@ class DeepArcManager {
   const std::vector<int>& pointPriorIndex() const { return pt_prior_index_; }
   const std::vector<double>& pointPriorMean() const { return pt_prior_mean_; }
   const std::vector<double>& pointPriorSqrtInfo() const { return pt_prior_sqrt_info_; }
+  // Gaussian priors on intrinsics for every later solve() of this manager (dab_set_intr_priors in
+  // dab.h; Ceres: NormalPrior(A, mu) with a NULL loss over the intrinsic's blocks [1] [2] [3]): a
+  // calibration with its covariance, for the groups setIntrinsicsFree frees. index in
+  // intrinsics(), mean [n][6] = (cx, cy, f0, f1, k0, k1), sqrt_info [n][6][6] row-major = A of the
+  // residual A (x - mean). Empty vectors clear them. Kept across the pipeline's re-set-ups beside
+  // the other priors and applied after every dab_set_problem; checked when the solve applies them
+  // to the handle. Slots the model lacks or the groups leave constant take no part, and without
+  // free groups (or under freeze_camera) the priors are ignored. Arrays whose lengths do not match
+  // index throw and leave the setting as it was.
+  void setIntrinsicPriors(const std::vector<int>& index, const std::vector<double>& mean,
+                          const std::vector<double>& sqrt_info) {
+    if (mean.size() != 6 * index.size() || sqrt_info.size() != 36 * index.size())
+      throw "intrinsic priors: mean needs 6 and sqrt_info 36 values per index";
+    intr_prior_index_ = index;
+    intr_prior_mean_ = mean;
+    intr_prior_sqrt_info_ = sqrt_info;
+  }
+  const std::vector<int>& intrinsicPriorIndex() const { return intr_prior_index_; }
+  const std::vector<double>& intrinsicPriorMean() const { return intr_prior_mean_; }
+  const std::vector<double>& intrinsicPriorSqrtInfo() const { return intr_prior_sqrt_info_; }
 
   // Covariance of the current scene at its current parameters (dab_covariance in dab.h: Sigma =
   // (J^T J)^-1 under this manager's loss, no sigma^2 factor; ceres::Covariance). The reference's
@@ -151,6 +171,8 @@ class DeepArcManager {
   std::vector<double> prior_mean_, prior_sqrt_info_;
   std::vector<int> pt_prior_index_;  // point priors (none), indices into point3d_
   std::vector<double> pt_prior_mean_, pt_prior_sqrt_info_;
+  std::vector<int> intr_prior_index_;  // intrinsic priors (none), indices into intrinsics_
+  std::vector<double> intr_prior_mean_, intr_prior_sqrt_info_;
   int arc_size_ = 0, ring_size_ = 0;
   bool share_extrinsic_ = false;
   std::map<int, std::map<int, Camera*> > hemisphere_;

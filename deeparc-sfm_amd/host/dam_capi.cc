@@ -192,6 +192,23 @@ int dam_set_point_priors(dam_manager* m, int32_t count, const int32_t* point_ind
   });
 }
 
+int dam_set_intr_priors(dam_manager* m, int32_t count, const int32_t* intr_index, const double* mean,
+                        const double* sqrt_info) {
+  return guarded([&] {
+    if (!m) throw "null manager";
+    if (count < 0) throw "negative prior count";
+    if (count > 0 && (!intr_index || !mean || !sqrt_info)) throw "null prior array";
+    const size_t n = (size_t)count;
+    const size_t nintr = m->m.intrinsics()->size();
+    for (size_t i = 0; i < n; ++i)
+      if (intr_index[i] < 0 || (size_t)intr_index[i] >= nintr) throw "prior on an intrinsic index out of range";
+    if (n == 0) m->m.setIntrinsicPriors({}, {}, {});
+    else
+      m->m.setIntrinsicPriors(std::vector<int>(intr_index, intr_index + n), std::vector<double>(mean, mean + 6 * n),
+                              std::vector<double>(sqrt_info, sqrt_info + 36 * n));
+  });
+}
+
 int dam_get_point_priors(dam_manager* m, int32_t* count, int32_t* point_index, double* mean, double* sqrt_info) {
   return guarded([&] {
     if (!m) throw "null manager";

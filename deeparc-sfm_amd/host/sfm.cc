@@ -57,6 +57,13 @@ int solveWith(DeepArcManager& m, const dab_options& options, bool freeze_camera,
                               m.pointPriorSqrtInfo().data());
   }
   if (rc) return rc;
+  // the intrinsic priors, or none: likewise after every (re-)set-up, after the groups above
+  {
+    const std::vector<int32_t> idx(m.intrinsicPriorIndex().begin(), m.intrinsicPriorIndex().end());
+    rc = dab_set_intr_priors(dh.h, (int32_t)idx.size(), idx.data(), m.intrinsicPriorMean().data(),
+                             m.intrinsicPriorSqrtInfo().data());
+  }
+  if (rc) return rc;
   const double t0 = dab_now_seconds();
   rc = dab_solve(dh.h, &options, s);
   // (not with free intrinsics: they need the exact step, and PCG's refusal would hide the reason)

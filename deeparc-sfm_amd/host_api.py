@@ -50,6 +50,7 @@ SIGNATURES = {
     "dam_set_ext_priors": (C.c_int, [C.c_void_p, C.c_int32, _ip, _dp, _dp]),
     "dam_set_point_priors": (C.c_int, [C.c_void_p, C.c_int32, _ip, _dp, _dp]),
     "dam_get_point_priors": (C.c_int, [C.c_void_p, _ip, _ip, _dp, _dp]),
+    "dam_set_intr_priors": (C.c_int, [C.c_void_p, C.c_int32, _ip, _dp, _dp]),
     "dam_covariance": (C.c_int, [C.c_void_p, _ip, C.c_int32, C.c_int32, _dp, _dp, _dp, _ip,
                                  C.POINTER(_abi.DabCovarianceInfo)]),
     "dam_covariance_intrinsics": (C.c_int, [C.c_void_p, _ip, C.c_int32, _dp, _dp, _dp, _dp, _ip, _ip,
@@ -194,6 +195,21 @@ class DeepArcManager:
         if mu.shape != (n, 3) or a.shape != (n, 3, 3):
             raise ValueError(f"mean: ({n}, 3) and sqrt_info: ({n}, 3, 3) values")
         _check(self.lib.dam_set_point_priors(self.h, n, _p(idx, C.c_int32), _p(mu, C.c_double), _p(a, C.c_double)))
+
+    def set_intr_priors(self, index, mean=None, sqrt_info=None):
+        """Gaussian priors on intrinsics for every later solve() of this manager
+        (dam_set_intr_priors; core.Solver.set_intr_priors' arguments, index in intrinsics()); None
+        or an empty index clears them."""
+        if index is None or np.size(index) == 0:
+            _check(self.lib.dam_set_intr_priors(self.h, 0, None, None, None))
+            return
+        idx = np.ascontiguousarray(index, np.int32).reshape(-1)
+        n = idx.shape[0]
+        mu = np.ascontiguousarray(mean, np.float64)
+        a = np.ascontiguousarray(sqrt_info, np.float64)
+        if mu.shape != (n, 6) or a.shape != (n, 6, 6):
+            raise ValueError(f"mean: ({n}, 6) and sqrt_info: ({n}, 6, 6) values")
+        _check(self.lib.dam_set_intr_priors(self.h, n, _p(idx, C.c_int32), _p(mu, C.c_double), _p(a, C.c_double)))
 
     def get_point_priors(self):
         """(index [n], mean [n][3], sqrt_info [n][3][3]) as the manager holds them now."""

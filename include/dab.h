@@ -490,6 +490,78 @@ int dab_get_point_priors(dab_handle* h, int32_t* count, int32_t* num_effective, 
                          double* sqrt_info);
 int dab_eval_point_priors(dab_handle* h, double* residuals /* [count][3], as set; nullable */, double* cost /* nullable */);
 
+/* ---- Gaussian priors on intrinsics -------------------------------------------------------
+ * "This calibration is known to within its certificate", between holding the intrinsics constant
+ * (the default) and freeing them (dab_set_intrinsics_free): what in Ceres is
+ *   problem.AddResidualBlock(new ceres::NormalPrior(A, mu), NULL, block)
+ * on an intrinsic's blocks. Ceres keeps three blocks, [1] (cx, cy), [2] (f0, f1), [3] (k0, k1);
+ * one 6x6 A over x_i = (cx, cy, f0, f1, k0, k1), dab_problem's slot layout, is the superset of
+ * them: a block-diagonal A is three NormalPriors, a full A carries a calibration's
+ * focal-distortion correlation. A prior on intrinsic i adds the residual block r = A (x_i - mu),
+ * x_i at the values on the handle (the refined ones), A = sqrt_info 6x6 row-major. Rows and
+ * columns of A may be zero. The prior adds 0.5 |r|^2 to every cost dab_solve and
+ * dab_covariance_intrinsics report and is never under the handle's robust loss (a NULL loss of
+ * its own). Uses: self-calibration from a calibration certificate, and the remedy for a problem
+ * that is rank deficient for the intrinsics alone (a camera with too few observations for its
+ * free intrinsic scalars).
+ *
+ * Inactive slots. A slot the model lacks (f1 with nf == 1, k beyond nk) or the mask leaves
+ * constant takes no part: its column of A and its entry of mu are dropped,
+ * r = A_act (x_act - mu_act). This is a deliberate simplification, the one below one level down:
+ * Ceres would carry the constant offset A_inact (x_inact - mu_inact) of a constant block. The
+ * values in A's inactive columns and mu's inactive entries change nothing, bitwise.
+ *
+ * The priors are state of the handle, like the loss, the masks and the other priors: set after
+ * dab_set_problem, which resets them to none (num_intr may change); they survive
+ * dab_update_parameters, dab_update_intrinsics, dab_set_loss, dab_set_intrinsics_free,
+ * dab_set_points_constant, dab_set_ext_priors and dab_set_point_priors and take effect at the next
+ * dab_solve or dab_covariance_intrinsics; dab_set_intrinsics_free after them changes the
+ * effective set at that call. count = 0 (arrays may be NULL) clears them. At most one prior per
+ * intrinsic. In a multi-rank handle every rank sets the same priors (intrinsics are replicated;
+ * the prior's sums are added once, after the sums over the ranks, identically on every rank).
+ *
+ * Effective set. A prior is effective when its intrinsic is in the free set the solve uses:
+ * referenced on some rank, at least one active scalar, freeze_camera not set: the set
+ * dab_get_intrinsics_free counts. Any other prior is ignored entirely: no cost, no residual rows,
+ * zeros from dab_eval_intr_priors (Ceres would carry the constant cost of such a block).
+ * *num_effective counts the effective priors (collective on a multi-rank handle with a non-empty
+ * mask, as dab_get_intrinsics_free is); dab_summary.num_residuals and
+ * dab_covariance_info.num_residuals grow by 6 per effective prior, num_parameters is unchanged.
+ * With no effective prior (never set, count 0, the mask all constant, only constant or
+ * unreferenced intrinsics named, freeze_camera) every call gives bitwise what it gives on a
+ * handle that never set one, and no prior kernel is launched. Plain dab_covariance is always in
+ * this case: it refuses a non-empty free set. The effective priors are ordered by intrinsic index,
+ * so the order they were set in changes nothing, bitwise.
+ *
+ * Where it enters: A^T A and A^T r are added to the intrinsic's U_zz | g_z after each evaluation
+ * and its all-reduce, so the Jacobi scale, the gradient norm, the bordered system of the exact
+ * step and dab_covariance_intrinsics take them with no other change (there are no new
+ * DAB_E_UNSUPPORTED cases: the refusals of a non-empty free set stay as they are); the model cost
+ * change and the candidate cost get the prior's terms after the candidate pass. Every prior sum
+ * has a fixed order: two solves agree bitwise.
+ *
+ * dab_get_intr_priors returns what was set (arrays nullable, sized by a first call for *count).
+ * dab_eval_intr_priors evaluates at the intrinsics now on the handle, for the mask now on it:
+ * residuals [count][6] in the order set, cost = 0.5 sum |r|^2 over the effective priors. On a
+ * multi-rank handle with priors set and a non-empty mask every rank calls it (it works out the
+ * free set as dab_solve does).
+ *
+ * dab_eval_residuals, dab_eval_jacobians, dab_eval_intrinsic_jacobians, dab_filter,
+ * dab_bench_eval_pass, dab_bench_get_blocks and dab_jacobian_bytes ignore these priors (raw
+ * observation quantities). dab_get_intrinsic_blocks reads U_zz | g_z where the last evaluation
+ * left them: raw after dab_bench_eval_pass, with A^T A | A^T r added after a dab_solve or a
+ * dab_covariance_intrinsics call with effective priors.
+ * Errors, all leaving the state unchanged: DAB_E_INVALID for a null handle (checked before any
+ * device use), count < 0, a null array with count > 0, an index outside [0, num_intr), a duplicate
+ * index, or a non-finite entry of mean or sqrt_info; DAB_E_STATE before dab_set_problem.
+ * dab_eval_intr_priors returns DAB_E_UNSUPPORTED for more than 16 free intrinsics, as dab_solve
+ * does. */
+int dab_set_intr_priors(dab_handle* h, int32_t count, const int32_t* intr_index /* [count] */,
+                        const double* mean /* [count][6] */, const double* sqrt_info /* [count][6][6] row-major */);
+int dab_get_intr_priors(dab_handle* h, int32_t* count, int32_t* num_effective, int32_t* intr_index, double* mean,
+                        double* sqrt_info);
+int dab_eval_intr_priors(dab_handle* h, double* residuals /* [count][6], as set; nullable */, double* cost /* nullable */);
+
 /* ---- evaluation (parity / filterPoint3d) ---------------------------------------------
  * residuals: [num_obs][2] in the caller's observation order.
  * jacobians: [num_obs][2][15] row-major, columns = [X(3) | w0(3) t0(3) | w1(3) t1(3)]
@@ -557,7 +629,9 @@ int dab_filter(dab_handle* h, double error_boundary, const double center[3], dou
  * (dab_set_points_constant: a ground-control point) or with one more constant extrinsic
  * (ext_const) beside the reference's arc 0 / camera 0; or, softly, with a position prior on one
  * or a few cameras (dab_set_ext_priors) or a prior on a few ground-control points
- * (dab_set_point_priors), whose uncertainty the covariance then carries.
+ * (dab_set_point_priors), whose uncertainty the covariance then carries. A deficiency of the
+ * intrinsics alone under dab_covariance_intrinsics (a camera with too few observations for its
+ * free scalars) has its own soft remedy: a calibration prior (dab_set_intr_priors).
  *
  * Multi-rank handles: every rank calls it. S is all-reduced as in the exact step, every rank
  * inverts its own copy (identical camera arrays) and gets the covariances of its own shard's

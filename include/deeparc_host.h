@@ -87,6 +87,18 @@ int dam_set_ext_priors(dam_manager* m, int32_t count, const int32_t* ext_index, 
 int dam_set_point_priors(dam_manager* m, int32_t count, const int32_t* point_index, const double* mean,
                          const double* sqrt_info);
 int dam_get_point_priors(dam_manager* m, int32_t* count, int32_t* point_index, double* mean, double* sqrt_info);
+/* Gaussian priors on intrinsics for every later solve of this manager (dab_set_intr_priors in
+ * dab.h; Ceres: NormalPrior(A, mu) with a NULL loss over the intrinsic's blocks [1] [2] [3]): a
+ * calibration with its covariance for the groups dam_set_intrinsics_free frees. intr_index
+ * [count] in the order of dam_get_cameras' intrinsics, mean [count][6] = (cx, cy, f0, f1, k0, k1),
+ * sqrt_info [count][6][6] row-major = A of the residual A (x - mean). count = 0 clears them. An
+ * index outside the manager's intrinsics, a negative count or a null array with count > 0 return
+ * an error and leave the setting as it was; duplicates and non-finite entries are refused by the
+ * solve that applies them. Re-applied after every re-set of the resident problem, like the other
+ * priors; slots the model lacks or the groups leave constant take no part, and without free groups
+ * the priors are ignored. */
+int dam_set_intr_priors(dam_manager* m, int32_t count, const int32_t* intr_index, const double* mean,
+                        const double* sqrt_info);
 /* DeepArcManager::covariance: dab_covariance (dab.h) of the manager's current scene at its
  * current parameters, under the manager's loss. extra_const[n_extra]: extrinsic indices held
  * constant beside the gauge rule's; the reference's rule leaves the rig's global scale free

@@ -24,6 +24,12 @@ single handle, on each rank those of the points it owns (Problem.shard_point_pri
 get at least one). A cost not summed over the ranks or a candidate term added after the sum shows
 as a cost difference far above --tol (the priors' share of the initial cost is printed and must be
 above 100 --tol). Off by default.
+--intr-priors calib, with --free-intrinsics, sets a full Gaussian prior on every intrinsic
+(dab_set_intr_priors: A = Q diag(1 / sigma) (I + 0.2 G), sigma = (2, 2, 5e-3 |f0|, 5e-3 |f1|, 5e-3,
+5e-3), mean = start + sigma o normal), the same on every rank's handle and on the single handle:
+intrinsics are replicated, so a prior added once per rank instead of once shows as a cost
+difference far above --tol (the priors' share of the initial cost is printed and must be above
+100 --tol). Off by default.
 --expect-auto-refused checks instead that LINEAR_SOLVER_AUTO, where it picks PCG (several ranks, a
 camera system that is not a small one), refuses a non-empty free set on every rank.
 --covariance checks dab_covariance instead: every rank calls it on its shard after the solve, and
@@ -81,6 +87,8 @@ def main():
                     help="Gaussian priors on every non-constant extrinsic, the same on every handle")
     ap.add_argument("--pt-priors", default="", choices=("", "all"),
                     help="Gaussian priors on every point, split over the ranks with the points")
+    ap.add_argument("--intr-priors", default="", choices=("", "calib"),
+                    help="with --free-intrinsics: Gaussian priors on every intrinsic, the same on every handle")
     ap.add_argument("--expect-auto-refused", action="store_true",
                     help="with --free-intrinsics: a rig whose tables do not fit the small-camera paths (135 "
                     "extrinsics), so AUTO picks PCG on several ranks; every rank's dab_solve must return "
@@ -291,8 +299,24 @@ def main():
             qa = np.stack([np.linalg.qr(rng.standard_normal((3, 3)))[0] @ np.diag(1.0 / sig)
                            @ (np.eye(3) + 0.2 * rng.standard_normal((3, 3))) for _ in qidx])
             pt_priors = (qidx, glob.points + 2.0 * sig * rng.standard_normal((len(qidx), 3)), qa)
+        intr_priors = None
+        if a.intr_priors:
+            if not a.free_intrinsics:
+                raise SystemExit("--intr-priors needs --free-intrinsics")
+            rng = np.random.default_rng(11)
+            zidx = np.arange(glob.intr.shape[0], dtype=np.int32)
+            za, zmu = [], []
+            for k6 in glob.intr:
+                sig = np.array([2.0, 2.0, 5e-3 * abs(k6[2]), 5e-3 * abs(k6[3]), 5e-3, 5e-3])
+                sig[sig == 0.0] = 1.0
+                q = np.linalg.qr(rng.standard_normal((6, 6)))[0]
+                za.append(q @ np.diag(1.0 / sig) @ (np.eye(6) + 0.2 * rng.standard_normal((6, 6))))
+                zmu.append(k6 + sig * rng.standard_normal(6))
+            intr_priors = (zidx, np.array(zmu), np.array(za))
         prior_share = 0.0
         pt_prior_share = 0.0
+        intr_prior_share = 0.0
+        intr_eff = (0, 0)
         pt_eff = (0, 0)
         live = []
         if a.live_together:  # every handle of this problem created (and its arena slot taken) up front
@@ -321,6 +345,9 @@ def main():
                 if pt_priors is not None:
                     s1.set_point_priors(*pt_priors)
                     pt_prior_share = s1.eval_point_priors()[1]
+                if intr_priors is not None:
+                    s1.set_intr_priors(*intr_priors)
+                    intr_prior_share = s1.eval_intr_priors()[1]
                 ropts = opts
                 if lst == pkg.DAB_LINEAR_SOLVER_AUTO:
                     # what AUTO must pick on several ranks: the exact step for small camera
@@ -331,6 +358,7 @@ def main():
                 ref = (s1.solve(ropts), g1.points.copy(), g1.ext.copy(), g1.intr.copy())
                 prior_share /= ref[0]["initial_cost"]
                 pt_prior_share /= ref[0]["initial_cost"]
+                intr_prior_share /= ref[0]["initial_cost"]
                 s1.close()
             dist.barrier()
             mine = glob.copy().shard(rank, world)
@@ -348,6 +376,9 @@ def main():
             if pt_priors is not None:
                 s.set_point_priors(*glob.shard_point_priors(pt_priors, rank, world))  # this rank's points' priors
                 pt_eff = (s.get_point_priors()[3], len(pt_priors[0]))
+            if intr_priors is not None:
+                s.set_intr_priors(*intr_priors)  # the same priors on every rank (include/dab.h)
+                intr_eff = (s.get_intr_priors()[3], len(intr_priors[0]))
             sched = s.eval_fused()
             p2p = s.comm_p2p()
             summ = s.solve(opts)
@@ -389,6 +420,7 @@ def main():
                     num_parameters=(summ["num_parameters"], rs["num_parameters"]),
                     num_residuals=(summ["num_residuals"], rs["num_residuals"], 2 * glob.num_obs), prior_share=prior_share,
                     pt_prior_share=pt_prior_share, pt_effective=pt_eff,
+                    intr_prior_share=intr_prior_share, intr_effective=intr_eff,
                     eval_schedule=sched, p2p=p2p,
                     assembly=(int(asm[0]), -int(asm[1]), rs["schur_assembly"]), const_held=bool(held.item()),
                     solver_used=(summ["linear_solver_type_used"], rs["linear_solver_type_used"]))
@@ -411,6 +443,8 @@ def main():
                or not v["const_held"]
                or (a.ext_priors and not (v["prior_share"] > 100 * a.tol and v["num_residuals"][1] > v["num_residuals"][2]))
                or (a.pt_priors and not (v["pt_prior_share"] > 100 * a.tol and 0 < v["pt_effective"][0] < v["pt_effective"][1]))
+               or (a.intr_priors and not (v["intr_prior_share"] > 100 * a.tol and v["intr_effective"][0] > 0
+                                          and v["num_residuals"][1] == v["num_residuals"][2] + 6 * v["intr_effective"][0]))
                or (a.const_points == "all" and v["solver_used"][0] == pkg.DAB_LINEAR_SOLVER_EXPLICIT_SCHUR
                    and v["assembly"] != (pkg.DAB_SCHUR_DIRECT,) * 3)
                or v["solver_used"][0] != v["solver_used"][1]]
