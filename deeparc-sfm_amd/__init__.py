@@ -10,6 +10,7 @@ from ._abi import (DAB_CONVERGENCE, DAB_E_INVALID, DAB_E_UNSUPPORTED, DAB_FAILUR
                    SIGNATURES, load_library, last_error)
 from ._abi import DabCovarianceInfo, DabCovarianceIntrInfo, DabCovarianceOptions
 from ._abi import DAB_INTR_CENTER, DAB_INTR_DISTORTION, DAB_INTR_FOCAL
+from ._abi import DAB_EXT_ROTATION, DAB_EXT_TRANSLATION
 from ._abi import DAB_SCHUR_DIRECT, DAB_SCHUR_PAIRS, DAB_SCHUR_TILES
 from .core import (CONFIGS, Problem, Solver, covariance_options, options, point_sqrt_info_from_sigmas, solve,
                    sqrt_info_from_sigmas, synth, synth_config)
@@ -23,6 +24,7 @@ __all__ = [
     "DAB_LOSS_TRIVIAL", "DAB_LOSS_HUBER", "DAB_LOSS_SOFT_L1", "DAB_LOSS_CAUCHY",
     "DAB_E_INVALID", "DAB_E_UNSUPPORTED",
     "DAB_INTR_CENTER", "DAB_INTR_FOCAL", "DAB_INTR_DISTORTION",
+    "DAB_EXT_ROTATION", "DAB_EXT_TRANSLATION",
     "DAB_SCHUR_PAIRS", "DAB_SCHUR_TILES", "DAB_SCHUR_DIRECT",
     "sqrt_info_from_sigmas", "point_sqrt_info_from_sigmas",
 ]

@@ -27,6 +27,8 @@ DAB_LOSS_CAUCHY = 3
 DAB_INTR_CENTER = 1
 DAB_INTR_FOCAL = 2
 DAB_INTR_DISTORTION = 4
+DAB_EXT_ROTATION = 0x07
+DAB_EXT_TRANSLATION = 0x38
 DAB_SCHUR_PAIRS = 0
 DAB_SCHUR_TILES = 1
 DAB_SCHUR_DIRECT = 2
@@ -163,6 +165,8 @@ SIGNATURES = {
     "dab_get_intrinsics_free": (C.c_int, [C.c_void_p, _u8p, _ip, _ip]),
     "dab_set_points_constant": (C.c_int, [C.c_void_p, _u8p]),
     "dab_get_points_constant": (C.c_int, [C.c_void_p, _u8p, _ip]),
+    "dab_set_ext_scalars_constant": (C.c_int, [C.c_void_p, _u8p]),
+    "dab_get_ext_scalars_constant": (C.c_int, [C.c_void_p, _u8p, _ip]),
     "dab_set_ext_priors": (C.c_int, [C.c_void_p, C.c_int32, _ip, _dp, _dp]),
     "dab_get_ext_priors": (C.c_int, [C.c_void_p, _ip, _ip, _ip, _dp, _dp]),
     "dab_eval_ext_priors": (C.c_int, [C.c_void_p, _dp, _dp]),

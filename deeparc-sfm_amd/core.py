@@ -333,6 +333,31 @@ class Solver:
         check(self.lib.dab_get_points_constant(self.h, _ptr(m, C.c_uint8), C.byref(n)), self.lib)
         return m, n.value
 
+    def set_ext_scalars_constant(self, bits):
+        """Which scalars of each extrinsic the next solve and covariance hold constant
+        (dab_set_ext_scalars_constant): bit k = scalar k of (w0,w1,w2,t0,t1,t2), DAB_EXT_ROTATION
+        7 | DAB_EXT_TRANSLATION 56, one int for every extrinsic or an array of num_ext; 0 / None =
+        none. Set after set_problem, which resets it; it survives every other setter. Bits on a
+        constant or unreferenced extrinsic are ignored."""
+        ne = int(self.problem.ext.shape[0])
+        if bits is None:
+            check(self.lib.dab_set_ext_scalars_constant(self.h, None), self.lib)
+            return
+        b = np.asarray(bits)
+        if b.ndim == 0:
+            b = np.full(ne, int(b))
+        if b.shape != (ne,) or (b < 0).any() or (b > 255).any():
+            raise ValueError(f"bits: one int or {ne} values in 0..63")
+        b = np.ascontiguousarray(b, np.uint8)
+        check(self.lib.dab_set_ext_scalars_constant(self.h, _ptr(b, C.c_uint8)), self.lib)
+
+    def get_ext_scalars_constant(self):
+        """(bits [num_ext] uint8 as set, effective constant scalars: those on free extrinsics)."""
+        b = np.zeros(int(self.problem.ext.shape[0]), np.uint8)
+        n = C.c_int32()
+        check(self.lib.dab_get_ext_scalars_constant(self.h, _ptr(b, C.c_uint8), C.byref(n)), self.lib)
+        return b, n.value
+
     def set_ext_priors(self, index, mean=None, sqrt_info=None):
         """Gaussian priors on extrinsics (dab_set_ext_priors; Ceres' NormalPrior(A, mu) with a NULL
         loss on the extrinsic's block): index [n] extrinsic indices, mean [n][6] in the library's
@@ -706,7 +731,7 @@ def point_sqrt_info_from_sigmas(sigma, n=None):
 
 def solve(problem, max_iteration=1000, max_second=3600, freeze_camera=False, device=0,
           verbose=False, loss=None, free_intrinsics=0, freeze_points=False, ext_priors=None, point_priors=None,
-          intr_priors=None, **opt_kw):
+          intr_priors=None, ext_scalars_constant=None, **opt_kw):
     """Drop-in for the reference's solve() (src/sfm.cc:31): DENSE_SCHUR-equivalent LM,
     max_num_iterations / max_solver_time_in_seconds as given, parameters updated in place.
     loss: None (the reference's NULL loss, sfm.cc:48) or a (kind, scale) pair such as
@@ -721,7 +746,10 @@ def solve(problem, max_iteration=1000, max_second=3600, freeze_camera=False, dev
     point_priors: None or (index, mean, sqrt_info), Gaussian priors on points, applied after
     freeze_points (Solver.set_point_priors; point_sqrt_info_from_sigmas builds the diagonal case).
     intr_priors: None or (index, mean, sqrt_info), Gaussian priors on the intrinsics that
-    free_intrinsics frees (Solver.set_intr_priors: a calibration with its covariance)."""
+    free_intrinsics frees (Solver.set_intr_priors: a calibration with its covariance).
+    ext_scalars_constant: None, or DAB_EXT_* bits (an int or one per extrinsic): the scalars of
+    the free extrinsics held constant (Solver.set_ext_scalars_constant), the equivalent of
+    keeping only one of sfm.cc:51-52 or of a SubsetManifold."""
     problem.freeze_camera = bool(freeze_camera)
     o = options(max_num_iterations=max_iteration, max_solver_time_in_seconds=float(max_second),
                 minimizer_progress_to_stdout=int(verbose), **opt_kw)
@@ -734,6 +762,8 @@ def solve(problem, max_iteration=1000, max_second=3600, freeze_camera=False, dev
             s.set_intrinsics_free(free_intrinsics)
         if np.any(np.asarray(freeze_points)):
             s.set_points_constant(freeze_points)
+        if ext_scalars_constant is not None:
+            s.set_ext_scalars_constant(ext_scalars_constant)
         if ext_priors is not None:
             s.set_ext_priors(*ext_priors)
         if point_priors is not None:

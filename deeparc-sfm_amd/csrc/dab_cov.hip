@@ -597,6 +597,9 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
   // constant points: PU = 0 and q = 0 take them out of S and of the fold-back (their rows of
   // point_cov come out exactly 0), and the rank test leaves them out
   CHECK_RC(pt_const_sync(h));
+  // constant scalars of an extrinsic: the Jacobi scale 0 empties their rows and columns of S, a
+  // unit diagonal keeps the factor, the rank test leaves them out and the outputs get exact zeros
+  CHECK_RC(ext_sub_sync(h));
   CHECK_RC(prior_sync(h));  // extrinsic priors: eval_jacobian_and_blocks folds them into U | g_c
   CHECK_RC(pt_prior_sync(h));  // point priors: ... into V | g, so the point factor and the rank test see them
   CHECK_RC(call_state(h, nullptr));  // whether any rank has one (several ranks: one small max-reduce)
@@ -619,7 +622,7 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
   out.first_deficient_point = -1;
   out.schur_assembly = h->schur_tiles ? DAB_SCHUR_TILES : DAB_SCHUR_PAIRS;
   out.num_residuals = 2 * h->N + 6 * h->n_prior + 3 * h->n_pt_prior + 6 * h->n_zprior;
-  out.num_parameters = 3 * nfree_pts + 6 * NC + cs.nz_scal;
+  out.num_parameters = 3 * nfree_pts + 6 * NC - h->n_ext_sub + cs.nz_scal;
   out.point_pivot_ratio_min = out.camera_pivot_ratio = std::numeric_limits<double>::quiet_NaN();
   for (hipEvent_t& e : h->cov_ev)
     if (!e) HIP_OK(hipEventCreate(&e));
@@ -719,9 +722,13 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
       CHECK_RC(intr_border_rows(h, nfi, sc, S_, ld_));
       HIP_OK(hipEventRecord(h->cov_ev_z[1], s));
     }
+    launch_ext_unit_diag(s, NC, h->d_exs, S_, ld_);
     if (chol_factor_solve(h->chol, s, n2, S_, ld_, cs.yc, h->d_flags + 1) != 0)
       return set_error(DAB_E_DEVICE, "dense Cholesky launch failed");
-    if (nfi > 0) launch_cov_diag_minmax_act(s, n2, n, h->lz.d_intr_act, chol_diag_blocks(h->chol), d_stat + 4);
+    if (h->d_exs)
+      launch_cov_diag_minmax_x(s, n2, n, nfi > 0 ? h->lz.d_intr_act : nullptr, h->d_exs, chol_diag_blocks(h->chol),
+                               d_stat + 4);
+    else if (nfi > 0) launch_cov_diag_minmax_act(s, n2, n, h->lz.d_intr_act, chol_diag_blocks(h->chol), d_stat + 4);
     else launch_cov_diag_minmax(s, n, chol_diag_blocks(h->chol), d_stat + 4);
   }
   HIP_OK(hipEventRecord(h->cov_ev[2], s));
@@ -811,6 +818,7 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
     }
     if (nfi > 0) launch_cov_unscale_z(s, NC, nfi, h->d_scale_c, h->lz.d_sz, h->lz.d_intr_act, S_, ld_, d_ext21);
     else launch_cov_unscale(s, NC, h->d_scale_c, h->d_S, h->lds, d_ext21);
+    launch_cov_zero_x(s, n2, n, h->d_exs, S_, ld_, d_ext21);
   }
   std::vector<double> hp;
   if (point_cov && NP > 0) {

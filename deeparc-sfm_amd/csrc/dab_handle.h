@@ -366,6 +366,15 @@ struct Handle {
   bool pt_const_dirty = false;            // lz.d_pt_const does not hold pt_const
   const uint8_t* d_ptc = nullptr;         // [NP] device point order (lz.d_pt_const), or null
   int n_pt_const = 0;                     // constant points of this rank (of the last sync)
+  // constant scalars of an extrinsic (dab_set_ext_scalars_constant). The mask is state of the
+  // handle, reset by dab_set_problem; empty = never set or NULL. ext_sub_sync works out the
+  // effective set (bits on an extrinsic with a camera column) at each call that honours it and
+  // leaves it per camera column in d_exs: null while the set is empty, so that every launch is
+  // then the unmasked one.
+  std::vector<uint8_t> ext_sub;           // [num_ext] bits as set
+  bool ext_sub_dirty = false;             // lz.d_ext_sub does not hold the effective set
+  const uint8_t* d_exs = nullptr;         // [NC] bits by camera column (lz.d_ext_sub), or null
+  int n_ext_sub = 0;                      // effective constant scalars (of the last sync)
   // extrinsic priors (dab_set_ext_priors), as set: state of the handle, reset by dab_set_problem.
   // prior_sync works out the effective set (the extrinsic has a camera column) at each call that
   // honours it and leaves its device records in lz.d_prior_*; n_prior = 0 while the set is empty,
@@ -419,6 +428,7 @@ struct Handle {
     int* d_ptmask = nullptr;  // [NP] free intrinsics each point sees (k_intr_ptmask, per solve)
     uint8_t* d_pt_const = nullptr;  // [NP] constant points, device point order (pt_const_sync)
     double* d_zero6 = nullptr;      // [6 NC] zeros: the rhs part of a step without free points
+    uint8_t* d_ext_sub = nullptr;   // [NC] constant scalars by camera column (ext_sub_sync)
     // effective extrinsic priors (prior_sync): (extrinsic, camera column) and kPriorRec doubles each
     int2* d_prior_idx = nullptr;
     double* d_prior_rec = nullptr;
@@ -707,6 +717,10 @@ int intr_eval(dab_handle* h);
 // ---- dab_problem.hip: constant points ----
 // the constant set of the mask on the handle -> h->d_ptc / h->n_pt_const (uploaded when changed)
 int pt_const_sync(dab_handle* h);
+
+// ---- dab_problem.hip: constant scalars of an extrinsic ----
+// the effective set of the mask on the handle -> h->d_exs / h->n_ext_sub (uploaded when changed)
+int ext_sub_sync(dab_handle* h);
 
 // ---- dab_problem.hip: extrinsic priors ----
 // the effective set of the priors on the handle -> lz.d_prior_* / h->n_prior (uploaded when changed)

@@ -328,6 +328,32 @@ void launch_cov_point_rank_m(hipStream_t s, int NP, const double* V, const doubl
 void launch_cam_block_solve(hipStream_t s, int NC, const double* ug, const double* scale_c, StepScalars sc,
                             double* yc, int* fail);
 
+// ---- constant scalars of an extrinsic (dab_set_ext_scalars_constant; dab_k_extsub.hip) -------
+// bits[NC], one byte per camera column: bit k = scalar k of (w0,w1,w2,t0,t1,t2) is constant. The
+// masked forms of the small camera-side kernels, launched only where the effective set is not
+// empty (null bits is the unmasked launch, or no launch for the fix-ups): a constant scalar gets
+// the Jacobi scale 0 (so its row and column of S, its rhs and its Y rows are exact zeros in every
+// assembly and product), x_c = x bitwise and delta = +0, no part in any norm, a unit diagonal in
+// front of every factor and preconditioner, no part in the covariance's camera rank test and exact
+// zeros in its outputs.
+void launch_scale_cams_x(hipStream_t s, int NC, const double* ug, double* scale_c, int on, const uint8_t* bits);
+void launch_cam_norms_x(hipStream_t s, int E, const int* ext_col, const double* ext, const double* ext_c,
+                        const double* ug, double* out, const uint8_t* bits);
+void launch_cam_candidate_x(hipStream_t s, int E, const int* ext_col, const double* ext, const double* yc,
+                            const double* scale_c, double* ext_c, double* delta_c, const uint8_t* bits);
+// S[t][t] = 1 for every constant scalar t < 6 NC of the dense system at ld
+void launch_ext_unit_diag(hipStream_t s, int NC, const uint8_t* bits, double* S, int ld);
+// the same on the PCG's [NC][36] operator and preconditioner blocks
+void launch_ext_unit_blocks(hipStream_t s, int NC, const uint8_t* bits, double* Ad, double* Minv);
+void launch_cam_block_solve_x(hipStream_t s, int NC, const double* ug, const double* scale_c, StepScalars sc,
+                              double* yc, int* fail, const uint8_t* bits);
+// launch_cov_diag_minmax(_act) without the constant scalars' unit rows (act nullable: no block z)
+void launch_cov_diag_minmax_x(hipStream_t s, int n, int n_ext, const int* act, const uint8_t* bits, const double* Ld,
+                              double* out);
+// +0 on the constant scalars' rows and columns of the unscaled C [n][n] and of the packed 6x6
+// diagonal blocks taken from it (nullable)
+void launch_cov_zero_x(hipStream_t s, int n, int n_ext, const uint8_t* bits, double* C, int ldc, double* blocks);
+
 // ---- extrinsic priors (dab_set_ext_priors; dab_k_prior.hip) ---------------------------------
 // The n effective priors, in the order they were set: idx[i] = (extrinsic, camera column) and
 // rec[i][kPriorRec] = mean (6) | A row-major (36) | A^T A upper-packed as ug packs U (21).

@@ -1323,6 +1323,68 @@ extern "C" int dab_get_points_constant(dab_handle* h, uint8_t* mask, int32_t* nu
 }
 
 // ------------------------------------------------------------------------------------
+// constant scalars of an extrinsic: host state
+// ------------------------------------------------------------------------------------
+// The effective set of the mask on the handle (bits on an extrinsic with a camera column:
+// referenced on some rank, not constant, no freeze_camera), by camera column, for the calls that
+// honour it. Empty: d_exs stays null and nothing touches the device.
+static int ext_sub_effective(const dab_handle* h, std::vector<uint8_t>* by_col) {
+  int n = 0;
+  if (h->ext_sub.empty()) return 0;
+  for (int e = 0; e < h->E; ++e) {
+    const int c = h->ext_col[(size_t)e];
+    if (c < 0) continue;
+    const uint8_t b = h->ext_sub[(size_t)e] & 63;
+    n += __builtin_popcount(b);
+    if (by_col) (*by_col)[(size_t)c] = b;
+  }
+  return n;
+}
+int dab::ext_sub_sync(dab_handle* h) {
+  h->d_exs = nullptr;
+  h->n_ext_sub = 0;
+  if (h->ext_sub.empty() || h->NC <= 0) return 0;
+  std::vector<uint8_t> m((size_t)h->NC, 0);
+  const int n = ext_sub_effective(h, &m);
+  if (n == 0) return 0;
+  if (!h->lz.d_ext_sub) {
+    CHECK_RC(h->dev.alloc(&h->lz.d_ext_sub, (size_t)h->NC));
+    h->ext_sub_dirty = true;
+  }
+  if (h->ext_sub_dirty) {
+    HIP_OK(hipMemcpyAsync(h->lz.d_ext_sub, m.data(), m.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));  // m goes out of scope
+    h->ext_sub_dirty = false;
+  }
+  h->d_exs = h->lz.d_ext_sub;
+  h->n_ext_sub = n;
+  return 0;
+}
+extern "C" int dab_set_ext_scalars_constant(dab_handle* h, const uint8_t* bits) {
+  clear_error();
+  if (!h) return set_error(DAB_E_INVALID, "null handle");
+  if (!h->have_problem) return set_error(DAB_E_STATE, "no problem set");
+  const size_t n = (size_t)h->prob.num_ext;
+  if (bits)
+    for (size_t e = 0; e < n; ++e)
+      if (bits[e] > 63) return set_error(DAB_E_INVALID, "extrinsic scalar bits above 63 (six scalars: bits 0..5)");
+  if (bits) h->ext_sub.assign(bits, bits + n);
+  else h->ext_sub.clear();
+  h->ext_sub_dirty = true;
+  return 0;
+}
+extern "C" int dab_get_ext_scalars_constant(dab_handle* h, uint8_t* bits, int32_t* num_constant_scalars) {
+  clear_error();
+  if (!h) return set_error(DAB_E_INVALID, "null handle");
+  if (!h->have_problem) return set_error(DAB_E_STATE, "no problem set");
+  const size_t n = (size_t)h->prob.num_ext;
+  if (bits)
+    for (size_t e = 0; e < n; ++e) bits[e] = h->ext_sub.empty() ? 0 : h->ext_sub[e];
+  if (num_constant_scalars) *num_constant_scalars = ext_sub_effective(h, nullptr);
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------
 // extrinsic priors: host state
 // ------------------------------------------------------------------------------------
 // The effective set of the priors on the handle (the extrinsic has a camera column: referenced on
@@ -1786,6 +1848,10 @@ static int set_problem_impl(dab_handle* h, const dab_problem* p) {
   h->pt_const_dirty = true;
   h->d_ptc = nullptr;
   h->n_pt_const = 0;
+  h->ext_sub.clear();  // every scalar free again (num_ext may have changed)
+  h->ext_sub_dirty = true;
+  h->d_exs = nullptr;
+  h->n_ext_sub = 0;
   h->prior_idx.clear();  // no priors (num_ext may have changed)
   h->prior_mean.clear();
   h->prior_A.clear();

@@ -76,6 +76,9 @@ static int pcg_solve(dab_handle* h, const dab_options& opt, StepScalars sc, YBuf
   launch_pcg_setup(s, NC, h->ug(), h->d_scale_c, sc, h->d_pcg_red, h->d_pcg_Ad, h->d_pcg_Minv, h->d_pcg_b,
                    h->d_yc, h->d_pcg_r, h->d_flags + 1);
   const int max_it = std::max(0, opt.max_linear_solver_iterations);
+  // constant scalars of an extrinsic: unit diagonal instead of min_lm_diagonal / radius in the
+  // operator's and the preconditioner's blocks (their rows and columns are exact zeros, b too)
+  launch_ext_unit_blocks(s, NC, h->d_exs, h->d_pcg_Ad, h->d_pcg_Minv);
   launch_pcg_init(s, NC, h->d_pcg_b, h->d_flags + 1, h->d_pcg_state, opt.eta, opt.min_linear_solver_iterations,
                   max_it, h->d_pcg_Minv, h->d_pcg_r, h->d_pcg_z, h->d_pcg_p);
   const int* xptr = h->nxlist > 0 ? h->d_xptr : nullptr;
@@ -255,8 +258,8 @@ int dab::eval_jacobian_and_blocks(dab_handle* h, bool with_norms, bool tables_cu
   if (with_norms) {
     launch_grad_points_m(s, h->NP, h->d_points, h->d_g, h->d_gpart, h->red_grid, h->d_ptc);
     launch_final_sum(s, h->red_grid, 3, h->d_gpart, h->d_scal + S_GMAX_P, 1u);
-    launch_cam_norms(s, h->E, h->d_ext_col, h->d_ext, nullptr, h->NC > 0 ? h->ug() : nullptr,
-                     h->d_scal + S_CAM0);
+    launch_cam_norms_x(s, h->E, h->d_ext_col, h->d_ext, nullptr, h->NC > 0 ? h->ug() : nullptr,
+                       h->d_scal + S_CAM0, h->d_exs);
   }
   // cross-rank: sums of cost, bad, gnorm, xnorm; max of gmax
   CHECK_RC(h->allreduce_cost());
@@ -319,7 +322,8 @@ void dab::launch_jacobi_scale(dab_handle* h, int nfi, int on) {
   const int NP = h->NP, NC = h->NC;
   if (h->d_ptc) launch_scale_points_m(s, NP, h->d_V, h->d_scale_p, on, h->d_ptc);
   else k_scale_points<<<grid_for(3 * NP, 256, 1 << 20), 256, 0, s>>>(NP, h->d_V, h->d_scale_p, on);
-  if (NC > 0) k_scale_cams<<<grid_for(6 * NC, 256, 1 << 20), 256, 0, s>>>(NC, h->ug(), h->d_scale_c, on);
+  if (h->d_exs) launch_scale_cams_x(s, NC, h->ug(), h->d_scale_c, on, h->d_exs);
+  else if (NC > 0) k_scale_cams<<<grid_for(6 * NC, 256, 1 << 20), 256, 0, s>>>(NC, h->ug(), h->d_scale_c, on);
   launch_intr_scale(s, nfi, h->lz.d_zg, h->lz.d_intr_act, h->lz.d_sz, on);
 }
 DAB_WARM_TU(k_scale_points);
@@ -528,6 +532,7 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
   HIP_OK(hipSetDevice(h->device));
   // constant points: this rank's set, and whether any rank has a free point left
   CHECK_RC(pt_const_sync(h));
+  CHECK_RC(ext_sub_sync(h));  // the effective constant scalars of the free extrinsics (none: no masked kernel)
   CHECK_RC(prior_sync(h));  // the effective extrinsic priors (none: no prior kernel is launched)
   CHECK_RC(pt_prior_sync(h));  // this rank's effective point priors, after pt_const_sync (likewise)
   // whether any rank has a free point left, and whether any has an effective point prior
@@ -550,7 +555,8 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
   // without cross blocks). Not with free intrinsics, nor for an explicitly requested PCG
   const bool direct = no_free_points && !use_pcg && cs.nfi == 0 && h->NC > 0 && h->knobs.points_direct != 0;
   const bool direct_dense = direct && h->ncross > 0;
-  const bool no_free_params = no_free_points && h->NC == 0;
+  // (or every scalar of every free extrinsic is constant, and no intrinsic is free)
+  const bool no_free_params = no_free_points && (h->NC == 0 || (h->n_ext_sub == 6 * h->NC && cs.nfi == 0));
   const double tp0 = now_s();
   if (direct_dense) {
     // the dense buffer as build_schur_tables sizes it (kept when the tables are built later)
@@ -591,7 +597,7 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
   sum->num_successful_steps = sum->num_unsuccessful_steps = 0;
   sum->num_iterations = 0;
   sum->num_residuals = 2 * h->N + 6 * h->n_prior + 3 * h->n_pt_prior + 6 * h->n_zprior;  // this rank's, as 2 N is
-  sum->num_parameters = 3 * (NP - h->n_pt_const) + 6 * NC + cs.nz_scal;
+  sum->num_parameters = 3 * (NP - h->n_pt_const) + 6 * NC - h->n_ext_sub + cs.nz_scal;
   sum->num_free_points = NP - h->n_pt_const;
   sum->num_free_ext = NC;
   sum->jacobian_evaluation_time_in_seconds = 0;
@@ -737,10 +743,11 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
     if (!direct) launch_point_factor_m(s, v, h->d_V, h->d_g, h->d_scale_p, sc, h->d_L, h->d_q, h->d_flags, h->d_ptc);
     bool pcg_fail = false;
     if (direct && !direct_dense) {
-      launch_cam_block_solve(s, NC, h->ug(), h->d_scale_c, sc, yc_, h->d_flags + 1);
+      launch_cam_block_solve_x(s, NC, h->ug(), h->d_scale_c, sc, yc_, h->d_flags + 1, h->d_exs);
     } else if (direct) {
       HIP_OK(hipMemsetAsync(cs.S, 0, sizeof(double) * (size_t)(n + 1) * cs.ld, s));
       launch_s_add_u(s, NC, h->ug(), h->ncross, h->d_cross_cam, h->Ux(), h->d_scale_c, sc, h->lz.d_zero6, cs.S, cs.ld);
+      launch_ext_unit_diag(s, NC, h->d_exs, cs.S, cs.ld);
       if (chol_factor_solve(h->chol, s, n, cs.S, cs.ld, yc_, h->d_flags + 1) != 0)
         return set_error(DAB_E_DEVICE, "dense Cholesky launch failed");
     } else if (NC > 0 && use_pcg) {
@@ -752,6 +759,7 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
     } else if (NC > 0) {
       CHECK_RC(cam_system_assemble(h, cs, sc, x_rhs, true));
       CHECK_RC(intr_border_rows(h, nfi, sc, cs.S, cs.ld));
+      launch_ext_unit_diag(s, NC, h->d_exs, cs.S, cs.ld);  // constant scalars: unit rows for the factor
       if (chol_factor_solve(h->chol, s, n2, cs.S, cs.ld, yc_, h->d_flags + 1) != 0)
         return set_error(DAB_E_DEVICE, "dense Cholesky launch failed");
     }
@@ -766,9 +774,9 @@ static int solve_impl(dab_handle* h, const dab_options* opt_in, dab_summary* sum
     // candidate x + delta and the model / candidate cost in one observation pass
     launch_axpy_points_m(s, NP, h->d_points, h->d_dp, h->d_points_c, h->d_gpart, h->red_grid, h->d_ptc);
     launch_final_sum(s, h->red_grid, 2, h->d_gpart, h->d_scal + S_STEP_P);
-    launch_cam_candidate(s, h->E, h->d_ext_col, h->d_ext, NC > 0 ? yc_ : nullptr, h->d_scale_c, h->d_ext_c,
-                         h->d_dc);
-    launch_cam_norms(s, h->E, h->d_ext_col, h->d_ext, h->d_ext_c, nullptr, h->d_scal + S_CAM0);
+    launch_cam_candidate_x(s, h->E, h->d_ext_col, h->d_ext, NC > 0 ? yc_ : nullptr, h->d_scale_c, h->d_ext_c,
+                           h->d_dc, h->d_exs);
+    launch_cam_norms_x(s, h->E, h->d_ext_col, h->d_ext, h->d_ext_c, nullptr, h->d_scal + S_CAM0, h->d_exs);
     launch_cam_tables(s, h->E, h->d_ext_c, h->d_camtab_c);
     const double tre = now_s();
     if (nfi > 0) {

@@ -4,6 +4,7 @@
 // on the GPU through libdab (dab_filter); the object-graph edits stay on the host, in
 // the reference's order, so the surviving blocks and points are the reference's.
 #pragma once
+#include <cstdint>
 #include <map>
 #include <memory>
 #include <string>
@@ -87,6 +88,21 @@ class DeepArcManager {
   const std::vector<int>& extrinsicPriorIndex() const { return prior_index_; }
   const std::vector<double>& extrinsicPriorMean() const { return prior_mean_; }
   const std::vector<double>& extrinsicPriorSqrtInfo() const { return prior_sqrt_info_; }
+  // Constant scalars of the extrinsics for every later solve() of this manager
+  // (dab_set_ext_scalars_constant in dab.h: one of sfm.cc:51-52 kept, or a SubsetManifold): bits
+  // indexed as extrinsics(), bit k = scalar k of (rotation, translation) is constant
+  // (DAB_EXT_ROTATION 0x07, DAB_EXT_TRANSLATION 0x38); an empty vector clears it. Kept across the
+  // pipeline's re-set-ups beside the loss and the other switches and applied after every
+  // dab_set_problem. A length other than extrinsics()->size() or a byte above 63 throws and
+  // leaves the setting as it was; bits on a constant extrinsic are ignored.
+  void setExtrinsicScalarsConstant(const std::vector<uint8_t>& bits) {
+    if (!bits.empty() && bits.size() != extrinsics()->size())
+      throw "constant extrinsic scalars: one byte per extrinsic";
+    for (uint8_t b : bits)
+      if (b > 63) throw "constant extrinsic scalars: bits above 63";
+    ext_scalars_const_ = bits;
+  }
+  const std::vector<uint8_t>& extrinsicScalarsConstant() const { return ext_scalars_const_; }
   // Gaussian priors on points for every later solve() of this manager (dab_set_point_priors in
   // dab.h; Ceres: problem.AddResidualBlock(new NormalPrior(A, mu), NULL, point)): ground-control
   // points. index into the manager's current point list (point3ds()), mean [n][3], sqrt_info
@@ -167,6 +183,7 @@ class DeepArcManager {
   double loss_scale_ = 1.0;
   int intr_free_ = 0;  // all constant (sfm.cc:60-62)
   bool points_const_ = false;  // all free (sfm.cc:59 commented out)
+  std::vector<uint8_t> ext_scalars_const_;  // none (every scalar of a free extrinsic is free)
   std::vector<int> prior_index_;  // extrinsic priors (none)
   std::vector<double> prior_mean_, prior_sqrt_info_;
   std::vector<int> pt_prior_index_;  // point priors (none), indices into point3d_

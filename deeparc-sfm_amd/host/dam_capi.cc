@@ -158,6 +158,14 @@ int dam_set_points_constant(dam_manager* m, int32_t all) {
   });
 }
 
+int dam_set_ext_scalars_constant(dam_manager* m, const uint8_t* bits) {
+  return guarded([&] {
+    if (!m) throw "null manager";
+    if (!bits) m->m.setExtrinsicScalarsConstant({});
+    else m->m.setExtrinsicScalarsConstant(std::vector<uint8_t>(bits, bits + m->m.extrinsics()->size()));
+  });
+}
+
 int dam_set_ext_priors(dam_manager* m, int32_t count, const int32_t* ext_index, const double* mean,
                        const double* sqrt_info) {
   return guarded([&] {

@@ -42,6 +42,13 @@ int solveWith(DeepArcManager& m, const dab_options& options, bool freeze_camera,
     rc = dab_set_points_constant(dh.h, nullptr);
   }
   if (rc) return rc;
+  // the constant scalars of the extrinsics, or none: after every (re-)set-up, which resets them
+  {
+    const std::vector<uint8_t>& bits = m.extrinsicScalarsConstant();
+    if (!bits.empty() && bits.size() != (size_t)scene.problem.num_ext) return DAB_E_INVALID;
+    rc = dab_set_ext_scalars_constant(dh.h, bits.empty() ? nullptr : bits.data());
+  }
+  if (rc) return rc;
   // the extrinsic priors, or none: after every (re-)set-up, which resets them on the handle
   {
     const std::vector<int32_t> idx(m.extrinsicPriorIndex().begin(), m.extrinsicPriorIndex().end());

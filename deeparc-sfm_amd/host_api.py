@@ -47,6 +47,7 @@ SIGNATURES = {
     "dam_set_loss": (C.c_int, [C.c_void_p, C.c_int32, C.c_double]),
     "dam_set_intrinsics_free": (C.c_int, [C.c_void_p, C.c_int32]),
     "dam_set_points_constant": (C.c_int, [C.c_void_p, C.c_int32]),
+    "dam_set_ext_scalars_constant": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8)]),
     "dam_set_ext_priors": (C.c_int, [C.c_void_p, C.c_int32, _ip, _dp, _dp]),
     "dam_set_point_priors": (C.c_int, [C.c_void_p, C.c_int32, _ip, _dp, _dp]),
     "dam_get_point_priors": (C.c_int, [C.c_void_p, _ip, _ip, _dp, _dp]),
@@ -165,6 +166,22 @@ class DeepArcManager:
         """Every later solve() of this manager holds all points constant (dam_set_points_constant):
         the reference's commented-out sfm.cc:59; False frees them again."""
         _check(self.lib.dam_set_points_constant(self.h, int(bool(all_points))))
+
+    def set_ext_scalars_constant(self, bits):
+        """Every later solve() of this manager holds these scalars of the extrinsics constant
+        (dam_set_ext_scalars_constant; core.Solver.set_ext_scalars_constant's argument, indexed as
+        cameras()' extrinsics): one int for every extrinsic or one byte each; None clears it."""
+        if bits is None:
+            _check(self.lib.dam_set_ext_scalars_constant(self.h, None))
+            return
+        ne = self.sizes()["extrinsics"]
+        b = np.asarray(bits)
+        if b.ndim == 0:
+            b = np.full(ne, int(b))
+        if b.shape != (ne,) or (b < 0).any() or (b > 255).any():
+            raise ValueError(f"bits: one int or {ne} values in 0..63")
+        b = np.ascontiguousarray(b, np.uint8)
+        _check(self.lib.dam_set_ext_scalars_constant(self.h, _p(b, C.c_uint8)))
 
     def set_ext_priors(self, index, mean=None, sqrt_info=None):
         """Gaussian priors on extrinsics for every later solve() of this manager

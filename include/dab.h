@@ -376,6 +376,63 @@ int dab_get_intrinsic_blocks(dab_handle* h, int32_t* num_free_intr, double* zg /
 int dab_set_points_constant(dab_handle* h, const uint8_t* mask /* [num_points], caller order; NULL = all free */);
 int dab_get_points_constant(dab_handle* h, uint8_t* mask /* nullable */, int32_t* num_constant /* nullable */);
 
+/* ---- constant scalars of an extrinsic ---------------------------------------------------
+ * ParameterBlock::get() hands Ceres an extrinsic as two blocks, rotation and translation, and
+ * sfm.cc:51-52 freezes them with two separate SetParameterBlockConstant lines; Ceres'
+ * SubsetManifold holds single coordinates constant. ext_const and freeze_camera know only "all
+ * or nothing". Here it is a mask on the handle, one byte per extrinsic, bit k = scalar k of
+ * ext[e] = (w0,w1,w2,t0,t1,t2) is constant (NULL = none, the default): the minimal hard gauge
+ * (camera 0 constant plus one translation coordinate of a second camera: 7 scalars, where one
+ * more constant extrinsic removes 6 degrees of freedom to fix one), a turntable ring whose
+ * translation is a design value, arc positions known from CAD, rotation-only or translation-only
+ * refinement.
+ *
+ * The mask is state of the handle, set after dab_set_problem; dab_set_problem resets it to none
+ * (num_ext may change); it survives dab_update_parameters and every other setter and takes effect
+ * at the next dab_solve, dab_covariance or dab_covariance_intrinsics. In a multi-rank handle
+ * every rank sets the same mask (extrinsics are replicated).
+ *
+ * Effective set. Only bits on an extrinsic of the free set count: referenced on some rank, not
+ * ext_const, freeze_camera not set; all other bits are ignored. dab_get_ext_scalars_constant
+ * returns the bytes as set (zeros when never set) and in *num_constant_scalars the effective
+ * bits. With no effective bit (never set, NULL, all zero, only constant or unreferenced
+ * extrinsics flagged, freeze_camera) every call gives bitwise what it gives on a handle that
+ * never set a mask, and no masked kernel is launched.
+ *
+ * A constant scalar is out of the problem, as a constant point is: it is not counted in
+ * num_parameters (dab_summary and both covariance infos), takes no part in gradient_max_norm,
+ * x_norm or step_norm, has no Jacobi scale or LM diagonal of its own, and is never written: its
+ * double in the caller's `ext` and in dab_get_parameters is bitwise the input, also after
+ * rejected steps and for an input of -0.0. Its observations keep every residual, cost and other
+ * column. Deliberate differences to Ceres' SubsetManifold: there x_norm runs over the ambient
+ * block and num_parameters counts ambient sizes; here both run over the free scalars.
+ *
+ * The camera set does not change: num_free_ext, the row order of ug, ext_cov, ext_full and
+ * cam_full and the Schur tables stay as they are. An extrinsic with all six bits set stays in
+ * the reduced system as six decoupled unit rows; ext_const is the way to take it out (the two
+ * solves agree to rounding). Every linear solver, assembly, loss, free-intrinsics, constant-
+ * points and prior combination that works without the mask works with it ("Constant
+ * scalars of an extrinsic"). No free parameter at all (every referenced point constant, every
+ * scalar of every free extrinsic constant, no free intrinsic): the "No non-constant parameter
+ * blocks found" summary described under constant points, the parameters untouched.
+ *
+ * Extrinsic priors keep Ceres' semantics: the residual is A (x_e - mu) over all six values; a
+ * constant scalar enters through the constant offset only, its column of A gives no gradient or
+ * curvature. dab_eval_ext_priors is unchanged.
+ *
+ * Covariance: Sigma is over the free scalars. Rows and columns of constant scalars in ext_cov,
+ * ext_full and cam_full are exactly 0 (known exactly, like inactive intrinsic slots), and they
+ * are left out of the camera rank test, like the unit rows of inactive intrinsic slots.
+ *
+ * dab_eval_residuals, dab_eval_jacobians, dab_eval_intrinsic_jacobians, dab_filter,
+ * dab_bench_eval_pass, dab_bench_get_blocks and dab_get_intrinsic_blocks ignore the mask (raw
+ * quantities). Errors, state unchanged: DAB_E_INVALID for a null handle (checked before any
+ * device use) or a byte above 63; DAB_E_STATE before dab_set_problem. */
+#define DAB_EXT_ROTATION    0x07  /* w0 w1 w2: block [4] / [6], sfm.cc:51 */
+#define DAB_EXT_TRANSLATION 0x38  /* t0 t1 t2: block [5] / [7], sfm.cc:52 */
+int dab_set_ext_scalars_constant(dab_handle* h, const uint8_t* bits /* [num_ext]; bit k = scalar k constant; NULL = none */);
+int dab_get_ext_scalars_constant(dab_handle* h, uint8_t* bits /* nullable */, int32_t* num_constant_scalars /* nullable */);
+
 /* ---- Gaussian priors on extrinsics ------------------------------------------------------
  * "This pose is known to within sigma", without holding it constant: what in Ceres is
  *   problem.AddResidualBlock(new ceres::NormalPrior(A, mu), NULL, ext)
@@ -627,7 +684,9 @@ int dab_filter(dab_handle* h, double error_boundary, const double center[3], dou
  * still sit in U and S would be overconfident. Remedies: drop such points from the problem
  * (Problem.subset in the Python layer), and fix the scale gauge with one constant point
  * (dab_set_points_constant: a ground-control point) or with one more constant extrinsic
- * (ext_const) beside the reference's arc 0 / camera 0; or, softly, with a position prior on one
+ * (ext_const) beside the reference's arc 0 / camera 0, or, minimally, with one constant
+ * translation coordinate of a second extrinsic (dab_set_ext_scalars_constant: the 7-scalar
+ * gauge; a rotation coordinate does not fix the scale); or, softly, with a position prior on one
  * or a few cameras (dab_set_ext_priors) or a prior on a few ground-control points
  * (dab_set_point_priors), whose uncertainty the covariance then carries. A deficiency of the
  * intrinsics alone under dab_covariance_intrinsics (a camera with too few observations for its

@@ -65,6 +65,13 @@ int dam_set_intrinsics_free(dam_manager* m, int32_t groups);
  * sfm.cc:59, all or nothing as that line is). 0, the default, frees them again. Re-applied after
  * every re-set of the resident problem, like the loss and the intrinsic groups. */
 int dam_set_points_constant(dam_manager* m, int32_t all);
+/* Constant scalars of the extrinsics for every later solve of this manager
+ * (dab_set_ext_scalars_constant in dab.h): bits [number of extrinsics], in the order of
+ * dam_get_cameras' extrinsics, bit k = scalar k of (rotation, translation) is constant
+ * (DAB_EXT_ROTATION 0x07, DAB_EXT_TRANSLATION 0x38); NULL clears it. A byte above 63 returns an
+ * error and leaves the setting as it was. Re-applied after every re-set of the resident problem,
+ * like the loss, the groups and the point flag; bits on a constant extrinsic are ignored. */
+int dam_set_ext_scalars_constant(dam_manager* m, const uint8_t* bits);
 /* Gaussian priors on extrinsics for every later solve of this manager (dab_set_ext_priors in
  * dab.h; Ceres: problem.AddResidualBlock(new NormalPrior(A, mu), NULL, ext)): ext_index [count]
  * in the order of dam_get_cameras' extrinsics, mean [count][6] = (rotation, translation),

@@ -15,6 +15,9 @@ step only: pair it with --solvers explicit).
 (dab_set_points_constant) on every rank's shard and on the single handle; the constant points must
 come back bitwise untouched, and with `all` every rank must report the direct camera step
 (DAB_SCHUR_DIRECT) for the explicit and the AUTO solver (pair it with --solvers explicit,auto).
+--ext-scalars rot-odd|trans-all|mix holds scalars of the extrinsics constant
+(dab_set_ext_scalars_constant; the masks of tests/extsub_ref.py), the same on every rank's handle and
+on the single handle; they must come back bitwise untouched on every rank.
 --ext-priors pose sets a full Gaussian prior on every non-constant extrinsic (dab_set_ext_priors),
 the same on every rank's handle and on the single handle: a prior added once per rank instead of
 once shows as a cost difference far above --tol (the priors' share of the initial cost is printed
@@ -83,6 +86,8 @@ def main():
     ap.add_argument("--const-points", default="", choices=("", "third", "all"),
                     help="constant points on every handle: every third point by global id, or all of them (then "
                     "every rank must take the direct camera step, S = U + D^2, also under AUTO)")
+    ap.add_argument("--ext-scalars", default="", choices=("", "rot-odd", "trans-all", "mix"),
+                    help="constant scalars of the extrinsics, the same bits on every handle")
     ap.add_argument("--ext-priors", default="", choices=("", "pose"),
                     help="Gaussian priors on every non-constant extrinsic, the same on every handle")
     ap.add_argument("--pt-priors", default="", choices=("", "all"),
@@ -281,6 +286,12 @@ def main():
             cmask = np.ones(glob.points.shape[0], bool)
             if a.const_points == "third":
                 cmask = np.arange(glob.points.shape[0]) % 3 == 0
+        ebits = None
+        if a.ext_scalars:
+            e = np.arange(glob.ext.shape[0])
+            ebits = {"rot-odd": np.where(e % 2 == 1, 7, 0), "trans-all": np.full(e.shape, 56),
+                     "mix": (37 * e + 11) & 63}[a.ext_scalars].astype(np.uint8)
+            eheld = ((ebits[:, None] >> np.arange(6)) & 1).astype(bool)
         priors = None
         if a.ext_priors:
             # A = Q D (I + 0.2 G), D = diag(1/0.02 x3, 1/0.05 x3); mean = start + sigma o normal
@@ -338,6 +349,9 @@ def main():
                     s1.set_intrinsics_free(a.free_intrinsics)
                 if cmask is not None:
                     s1.set_points_constant(cmask)
+                if ebits is not None:
+                    s1.set_ext_scalars_constant(ebits)
+                    assert s1.get_ext_scalars_constant()[1] > 0
                 if priors is not None:
                     s1.set_ext_priors(*priors)
                     assert s1.get_ext_priors()[3] == len(priors[0])
@@ -371,6 +385,8 @@ def main():
                 s.set_intrinsics_free(a.free_intrinsics)  # the same mask on every rank (include/dab.h)
             if cmask is not None:
                 s.set_points_constant(cmask)  # the shard's points are the ones this rank references
+            if ebits is not None:
+                s.set_ext_scalars_constant(ebits)  # the same bits on every rank (include/dab.h)
             if priors is not None:
                 s.set_ext_priors(*priors)  # the same priors on every rank (include/dab.h)
             if pt_priors is not None:
@@ -397,6 +413,8 @@ def main():
             asm = torch.tensor([summ["schur_assembly"], -summ["schur_assembly"]], dtype=torch.int32)
             dist.all_reduce(asm, op=dist.ReduceOp.MAX)  # (max, -min) over the ranks
             held = True if cmask is None else bool(np.array_equal(mine.points[cmask], glob.points[cmask]))
+            if ebits is not None:
+                held = held and mine.ext[eheld].tobytes() == glob.ext[eheld].tobytes()
             held = torch.tensor([1 if held else 0], dtype=torch.int32)
             dist.all_reduce(held, op=dist.ReduceOp.MIN)
             if rank == 0:
