@@ -8,7 +8,7 @@ from ._abi import (DAB_CONVERGENCE, DAB_E_INVALID, DAB_E_UNSUPPORTED, DAB_FAILUR
                    DAB_LINEAR_SOLVER_EXPLICIT_SCHUR, DAB_LINEAR_SOLVER_IMPLICIT_SCHUR_PCG, DAB_LOSS_CAUCHY,
                    DAB_LOSS_HUBER, DAB_LOSS_SOFT_L1, DAB_LOSS_TRIVIAL, DAB_NO_CONVERGENCE, LIB_PATH,
                    SIGNATURES, load_library, last_error)
-from ._abi import DabCovarianceInfo, DabCovarianceIntrInfo, DabCovarianceOptions
+from ._abi import DabCovBlocksRequest, DabCovarianceInfo, DabCovarianceIntrInfo, DabCovarianceOptions
 from ._abi import DAB_INTR_CENTER, DAB_INTR_DISTORTION, DAB_INTR_FOCAL
 from ._abi import DAB_EXT_ROTATION, DAB_EXT_TRANSLATION
 from ._abi import DAB_SCHUR_DIRECT, DAB_SCHUR_PAIRS, DAB_SCHUR_TILES
@@ -18,6 +18,7 @@ from .core import (CONFIGS, Problem, Solver, covariance_options, options, point_
 __all__ = [
     "CONFIGS", "Problem", "Solver", "options", "solve", "synth", "synth_config",
     "covariance_options", "DabCovarianceOptions", "DabCovarianceInfo", "DabCovarianceIntrInfo",
+    "DabCovBlocksRequest",
     "load_library", "last_error", "LIB_PATH", "SIGNATURES",
     "DAB_CONVERGENCE", "DAB_NO_CONVERGENCE", "DAB_FAILURE",
     "DAB_LINEAR_SOLVER_EXPLICIT_SCHUR", "DAB_LINEAR_SOLVER_IMPLICIT_SCHUR_PCG", "DAB_LINEAR_SOLVER_AUTO",

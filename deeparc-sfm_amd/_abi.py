@@ -126,6 +126,11 @@ class DabCovarianceIntrInfo(C.Structure):
                 ("border_ms", C.c_double), ("reserved", C.c_double)]
 
 
+class DabCovBlocksRequest(C.Structure):
+    _fields_ = [("num_pp", C.c_int32), ("pp", _ip), ("num_pe", C.c_int32), ("pe", _ip),
+                ("num_pz", C.c_int32), ("pz", _ip)]
+
+
 COV_STATUS = {0: "OK", 1: "RANK_DEFICIENT"}
 
 
@@ -185,6 +190,9 @@ SIGNATURES = {
                                  C.POINTER(DabCovarianceInfo)]),
     "dab_covariance_intrinsics": (C.c_int, [C.c_void_p, C.POINTER(DabCovarianceOptions), _dp, _dp, _dp, _dp,
                                             C.POINTER(DabCovarianceInfo), C.POINTER(DabCovarianceIntrInfo)]),
+    "dab_covariance_blocks": (C.c_int, [C.c_void_p, C.POINTER(DabCovarianceOptions), C.POINTER(DabCovBlocksRequest),
+                                        _dp, _dp, _dp, C.POINTER(DabCovarianceInfo),
+                                        C.POINTER(DabCovarianceIntrInfo), _dp]),
     "dab_eval_residuals": (C.c_int, [C.c_void_p, _dp, _dp]),
     "dab_eval_jacobians": (C.c_int, [C.c_void_p, _dp, _dp]),
     "dab_filter": (C.c_int, [C.c_void_p, C.c_double, _dp, C.c_double, _u8p, _u8p, _ip, _ip]),

@@ -611,6 +611,53 @@ class Solver:
                     intr_cov=_unpack_sym(zc, 6) if ok else None, intr_index=self._intr_index(nfi),
                     cam_full=cf if ok and full else None)
 
+    def covariance_blocks(self, pp=None, pe=None, pz=None, **opts):
+        """Cross blocks of Sigma for lists of pairs (dab_covariance_blocks): `pp` (n, 2) point ids
+        (a, b), `pe` (n, 2) (point id, extrinsic index), `pz` (n, 2) (point id, intrinsic index).
+        Sigma is covariance()'s on a handle without free intrinsics and covariance(intrinsics=
+        True)'s on one with them. Returns a dict with `info` (as covariance() returns it, with
+        num_free_intr, num_free_scalars, border_ms and blocks_ms, the device time of the
+        cross-block kernels) and `pp` (n, 3, 3), `pe` (n, 3, 6) over (w0, w1, w2, t0, t1, t2), `pz`
+        (n, 3, 6) over (cx, cy, f0, f1, k0, k1); None for a list that was not given and for all
+        three when info["status"] is "RANK_DEFICIENT". Blocks known exactly (a constant point, a
+        constant extrinsic or scalar, an intrinsic or slot that is not free) are 0, blocks without
+        information (a point this handle does not reference) NaN.
+
+        The variance of the distance between the points a and b:
+
+            c = s.covariance(ext=False)["point_cov"]
+            x = s.covariance_blocks(pp=[(a, b)])["pp"][0]
+            u = (X[a] - X[b]) / np.linalg.norm(X[a] - X[b])
+            var = u @ (c[a] + c[b] - x - x.T) @ u        # times 2 cost / dof for sigma^2
+        """
+        o = covariance_options(**opts)
+        info, zinfo = DabCovarianceInfo(), DabCovarianceIntrInfo()
+        req = _abi.DabCovBlocksRequest()
+        keep, outs = [], {}
+        for name, width in (("pp", 9), ("pe", 18), ("pz", 18)):
+            lst = {"pp": pp, "pe": pe, "pz": pz}[name]
+            if lst is None:
+                outs[name] = None
+                continue
+            idx = np.ascontiguousarray(np.asarray(lst, np.int32).reshape(-1, 2))
+            keep.append(idx)
+            outs[name] = np.zeros((idx.shape[0], width))
+            setattr(req, "num_" + name, idx.shape[0])
+            setattr(req, name, _ptr(idx, C.c_int32))
+        ms = C.c_double(0.0)
+        check(self.lib.dab_covariance_blocks(self.h, C.byref(o), C.byref(req), _ptr(outs["pp"], C.c_double),
+                                             _ptr(outs["pe"], C.c_double), _ptr(outs["pz"], C.c_double),
+                                             C.byref(info), C.byref(zinfo), C.byref(ms)), self.lib)
+        d = {k: getattr(info, k) for k, _ in DabCovarianceInfo._fields_}
+        d.update({k: getattr(zinfo, k) for k in ("num_free_intr", "num_free_scalars", "border_ms")})
+        d["blocks_ms"] = ms.value
+        d["status"] = _abi.COV_STATUS.get(info.status, str(info.status))
+        ok = info.status == 0
+        shape = {"pp": (3, 3), "pe": (3, 6), "pz": (3, 6)}
+        res = {k: (v.reshape((-1,) + shape[k]) if ok and v is not None else None) for k, v in outs.items()}
+        res["info"] = d
+        return res
+
     def residuals(self):
         r = np.zeros((self.problem.num_obs, 2))
         cost = C.c_double()

@@ -568,9 +568,166 @@ using namespace dab;
 // border rows of one undamped LM step; C' = S'^-1, s = (s_c, s_z), and a point's fold-back gains
 // one record Gz_p,i per free intrinsic it sees (k_cov_gz). With nfi = 0 every launch and buffer
 // is dab_covariance's. ext_full: [n'][n'] then, intr_cov [nfi][21].
+//
+// xb (dab_covariance_blocks): cross blocks for the request's pairs, folded from the same C and the
+// same record store by the kernels of dab_k_covx.hip, after the point blocks and before the
+// unscale. With xb null or empty every launch and buffer is as without it.
+namespace {
+struct CovBlocks {
+  const dab_cov_blocks_request* req = nullptr;
+  double *pp = nullptr, *pe = nullptr, *pz = nullptr;
+  double* ms = nullptr;
+  bool any() const { return req && (req->num_pp > 0 || req->num_pe > 0 || req->num_pz > 0); }
+};
+// how each pair is answered
+enum : uint8_t { kXDev = 0, kXDevT = 1, kXZero = 2, kXNan = 3 };
+struct CovxPlan {
+  std::vector<int2> pairs;   // [pp | pe | pz] device pairs; x < 0: answered on the host
+  std::vector<uint8_t> how;  // [pp | pe | pz]
+  std::vector<double> out;   // [pp 9 | pe 18 | pz 18 each] as the device left them
+};
+// where the fold-back's records are (launch_cov_points / launch_cov_points_z)
+struct CovRecs {
+  bool with_recs = false;
+  const int *rbase = nullptr, *rcnt = nullptr, *rcam = nullptr;
+  const double* rec = nullptr;
+  const double* C = nullptr;
+  int ldc = 0;
+};
+}  // namespace
+
+// the request's lists and indices, before anything on the handle changes
+static int cov_blocks_check(const dab_handle* h, const CovBlocks& xb) {
+  const dab_cov_blocks_request& r = *xb.req;
+  if (r.num_pp < 0 || r.num_pe < 0 || r.num_pz < 0) return set_error(DAB_E_INVALID, "negative pair count");
+  if ((r.num_pp > 0 && (!r.pp || !xb.pp)) || (r.num_pe > 0 && (!r.pe || !xb.pe)) ||
+      (r.num_pz > 0 && (!r.pz || !xb.pz)))
+    return set_error(DAB_E_INVALID, "a pair list with a null index or output array");
+  const int npts = h->prob.num_points, E = h->E, NI = h->NI;
+  for (int i = 0; i < 2 * r.num_pp; ++i)
+    if (r.pp[i] < 0 || r.pp[i] >= npts) return set_error(DAB_E_INVALID, "pp: point index out of range");
+  for (int i = 0; i < r.num_pe; ++i) {
+    if (r.pe[2 * i] < 0 || r.pe[2 * i] >= npts) return set_error(DAB_E_INVALID, "pe: point index out of range");
+    if (r.pe[2 * i + 1] < 0 || r.pe[2 * i + 1] >= E)
+      return set_error(DAB_E_INVALID, "pe: extrinsic index out of range");
+  }
+  for (int i = 0; i < r.num_pz; ++i) {
+    if (r.pz[2 * i] < 0 || r.pz[2 * i] >= npts) return set_error(DAB_E_INVALID, "pz: point index out of range");
+    if (r.pz[2 * i + 1] < 0 || r.pz[2 * i + 1] >= NI)
+      return set_error(DAB_E_INVALID, "pz: intrinsic index out of range");
+  }
+  return 0;
+}
+
+// Translate the pairs (caller's ids -> device points and column blocks), upload them once and
+// launch the two kernels between cov_ev_x[0] and [1]; the blocks come back into plan.out on the
+// stream (the caller synchronises). A pair with a point this rank does not reference, or with a
+// free extrinsic nothing references, carries no information (NaN); else one with a constant
+// point, a constant extrinsic or an intrinsic outside the free set is known exactly (+0).
+static int cov_blocks_run(dab_handle* h, const CovBlocks& xb, int nfi, const CovRecs& rc, CovxPlan* plan) {
+  const dab_cov_blocks_request& r = *xb.req;
+  const int NP = h->NP, NC = h->NC;
+  hipStream_t s = h->stream;
+  const size_t npp = (size_t)r.num_pp, npe = (size_t)r.num_pe, npz = (size_t)r.num_pz, nall = npp + npe + npz;
+  std::vector<int> dev_of((size_t)std::max(1, h->prob.num_points), -1);
+  for (int i = 0; i < NP; ++i) dev_of[(size_t)h->pt_of[(size_t)i]] = i;
+  const bool any_const = h->d_ptc != nullptr && !h->pt_const.empty();
+  auto is_const = [&](int id) { return any_const && h->pt_const[(size_t)id] != 0; };
+  plan->pairs.assign(nall, make_int2(-1, -1));
+  plan->how.assign(nall, kXNan);
+  for (size_t i = 0; i < npp; ++i) {
+    const int a = r.pp[2 * i], b = r.pp[2 * i + 1];
+    const int da = dev_of[(size_t)a], db = dev_of[(size_t)b];
+    if (da < 0 || db < 0) continue;
+    if (is_const(a) || is_const(b)) {
+      plan->how[i] = kXZero;
+      continue;
+    }
+    plan->pairs[i] = make_int2(std::min(da, db), std::max(da, db));
+    plan->how[i] = da <= db ? kXDev : kXDevT;
+  }
+  for (size_t i = 0; i < npe; ++i) {
+    const int a = r.pe[2 * i], e = r.pe[2 * i + 1];
+    const int da = dev_of[(size_t)a], c = h->ext_col[(size_t)e];
+    if (da < 0 || (c < 0 && !h->ext_fixed[(size_t)e])) continue;
+    if (c < 0 || is_const(a) || !rc.with_recs) {
+      plan->how[npp + i] = kXZero;
+      continue;
+    }
+    plan->pairs[npp + i] = make_int2(da, c);
+    plan->how[npp + i] = kXDev;
+  }
+  for (size_t i = 0; i < npz; ++i) {
+    const int a = r.pz[2 * i], z = r.pz[2 * i + 1];
+    const int da = dev_of[(size_t)a];
+    if (da < 0) continue;
+    const int zi = nfi > 0 ? h->intr_meta[(size_t)z].x : -1;
+    if (zi < 0 || is_const(a) || !rc.with_recs) {
+      plan->how[npp + npe + i] = kXZero;
+      continue;
+    }
+    plan->pairs[npp + npe + i] = make_int2(da, NC + zi);
+    plan->how[npp + npe + i] = kXDev;
+  }
+  const size_t nout = 9 * npp + 18 * (npe + npz);
+  if (nall > h->lz.covx_pairs_cap) {
+    h->dev.drop(h->lz.d_covx_pairs);
+    h->lz.d_covx_pairs = nullptr;
+    h->lz.covx_pairs_cap = 0;
+    CHECK_RC(h->dev.alloc(&h->lz.d_covx_pairs, nall));
+    h->lz.covx_pairs_cap = nall;
+  }
+  if (nout > h->lz.covx_out_cap) {
+    h->dev.drop(h->lz.d_covx_out);
+    h->lz.d_covx_out = nullptr;
+    h->lz.covx_out_cap = 0;
+    CHECK_RC(h->dev.alloc(&h->lz.d_covx_out, nout));
+    h->lz.covx_out_cap = nout;
+  }
+  int2* const d_pairs = h->lz.d_covx_pairs;
+  double* const d_out = h->lz.d_covx_out;
+  HIP_OK(hipMemcpyAsync(d_pairs, plan->pairs.data(), sizeof(int2) * nall, hipMemcpyHostToDevice, s));
+  HIP_OK(hipEventRecord(h->cov_ev_x[0], s));
+  launch_covx_pp(s, (int)npp, d_pairs, rc.with_recs, rc.rbase, rc.rcnt, rc.rec, rc.rcam, h->d_L, rc.C, rc.ldc, d_out);
+  if (rc.with_recs) {
+    launch_covx_pc(s, (int)npe, d_pairs + npp, rc.rbase, rc.rcnt, rc.rec, rc.rcam, h->d_L, rc.C, rc.ldc, NC,
+                   h->d_scale_c, h->lz.d_sz, d_out + 9 * npp);
+    launch_covx_pc(s, (int)npz, d_pairs + npp + npe, rc.rbase, rc.rcnt, rc.rec, rc.rcam, h->d_L, rc.C, rc.ldc, NC,
+                   h->d_scale_c, h->lz.d_sz, d_out + 9 * npp + 18 * npe);
+  }
+  HIP_OK(hipEventRecord(h->cov_ev_x[1], s));
+  plan->out.resize(nout);
+  HIP_OK(hipMemcpyAsync(plan->out.data(), d_out, sizeof(double) * nout, hipMemcpyDeviceToHost, s));
+  return 0;
+}
+
+// the caller's arrays from the plan, after the last check that can fail
+static void cov_blocks_write(const CovBlocks& xb, const CovxPlan& plan) {
+  const dab_cov_blocks_request& r = *xb.req;
+  const size_t npp = (size_t)r.num_pp, npe = (size_t)r.num_pe, npz = (size_t)r.num_pz;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  for (size_t i = 0; i < npp; ++i) {
+    double* o = xb.pp + 9 * i;
+    const double* d = plan.out.data() + 9 * i;
+    const uint8_t how = plan.how[i];
+    for (int a = 0; a < 3; ++a)
+      for (int b = 0; b < 3; ++b)
+        o[3 * a + b] = how == kXDev ? d[3 * a + b] : how == kXDevT ? d[3 * b + a] : how == kXZero ? 0.0 : nan;
+  }
+  auto rect = [&](size_t n, size_t first, const double* d, double* o) {
+    for (size_t i = 0; i < n; ++i) {
+      const uint8_t how = plan.how[first + i];
+      if (how == kXDev) std::memcpy(o + 18 * i, d + 18 * i, 18 * sizeof(double));
+      else std::fill(o + 18 * i, o + 18 * i + 18, how == kXZero ? 0.0 : nan);
+    }
+  };
+  rect(npe, npp, plan.out.data() + 9 * npp, xb.pe);
+  rect(npz, npp + npe, plan.out.data() + 9 * npp + 18 * npe, xb.pz);
+}
+
 static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, double* point_cov, double* ext_cov,
                            double* intr_cov, double* ext_full, dab_covariance_info* info,
-                           dab_covariance_intr_info* zinfo, bool with_intr) {
+                           dab_covariance_intr_info* zinfo, bool with_intr, const CovBlocks* xb = nullptr) {
   if (!with_intr && h && h->have_problem && intr_mask_any(h)) {
     // free intrinsics are not part of the covariance: it would report them as exactly known
     int nfi_cov = 0;
@@ -587,9 +744,11 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
   else dab_covariance_options_init(&opt);
   if (!(std::isfinite(opt.min_pivot_ratio) && opt.min_pivot_ratio > 0.0))
     return set_error(DAB_E_INVALID, "min_pivot_ratio must be finite and > 0");
-  if (!info && !point_cov && !ext_cov && !intr_cov && !ext_full)
+  const bool want_x = xb && xb->any();
+  if (!info && !point_cov && !ext_cov && !intr_cov && !ext_full && !want_x)
     return set_error(DAB_E_INVALID, "null info and null arrays");
   if (!h->have_problem) return set_error(DAB_E_STATE, "no problem set");
+  if (want_x) CHECK_RC(cov_blocks_check(h, *xb));
   HIP_OK(hipSetDevice(h->device));
   // free intrinsics: dab_solve's rule and refusals, before anything on the handle changes
   CamSystem cs;
@@ -628,6 +787,9 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
     if (!e) HIP_OK(hipEventCreate(&e));
   if (nfi > 0)
     for (hipEvent_t& e : h->cov_ev_z)
+      if (!e) HIP_OK(hipEventCreate(&e));
+  if (want_x)
+    for (hipEvent_t& e : h->cov_ev_x)
       if (!e) HIP_OK(hipEventCreate(&e));
   const int rgrid = cov_rank_grid(NP);
   if (!h->lz.d_cov_stat) CHECK_RC(h->dev.alloc(&h->lz.d_cov_stat, (size_t)8 + 2 * (size_t)rgrid));
@@ -713,7 +875,7 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
     if (h->schur_tiles) {
       // the point kernel reads per-entry records: the tile path keeps per-(point, camera) sums only
       if (!h->lz.d_Yrec) CHECK_RC(h->dev.alloc(&h->lz.d_Yrec, (size_t)kYRec * std::max(1, h->NE)));
-      if (point_cov)
+      if (point_cov || want_x)
         launch_entry_y(s, v, h->d_points, h->d_camtab, h->d_scale_c, h->d_L, YBufs{h->d_Y, h->d_Yp, false}, false,
                        h->lz.d_Yrec);
     }
@@ -747,10 +909,10 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
       return finish(h->cov_ev[2]);
     }
   }
-  if (!point_cov && !ext_cov && !intr_cov && !ext_full) return finish(h->cov_ev[2]);  // the size / rank query
+  if (!point_cov && !ext_cov && !intr_cov && !ext_full && !want_x) return finish(h->cov_ev[2]);  // the size / rank query
 
   // ---- C = S^-1 from the factor, the point blocks, the unscaled camera part ----
-  const bool want_c = NC > 0 && (point_cov || ext_cov || intr_cov || ext_full);
+  const bool want_c = NC > 0 && (point_cov || ext_cov || intr_cov || ext_full || want_x);
   if (want_c && nfi > 0) {
     // the second n' x n' buffer (n' changes with the free set: kept while it fits)
     const size_t need = (size_t)n2 * ld_;
@@ -767,7 +929,8 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
     launch_cov_inverse(s, n, h->d_S, h->lds, chol_diag_blocks(h->chol), h->lz.d_covZ, h->lds, h->d_S, h->lds);
   }
   HIP_OK(hipEventRecord(h->cov_ev[3], s));
-  if (point_cov) {
+  CovRecs xr;  // the cross blocks read the record store the point blocks leave
+  if (point_cov || want_x) {
     if (!h->lz.d_cov_pts) CHECK_RC(h->dev.alloc(&h->lz.d_cov_pts, (size_t)6 * std::max(1, NP)));
     if (!h->lz.d_cov_idx) CHECK_RC(h->dev.alloc(&h->lz.d_cov_idx, (size_t)std::max(1, h->NE) + (size_t)std::max(1, NP)));
     if (nfi > 0) {
@@ -803,13 +966,18 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
                           h->lz.d_cov_idx, h->lz.d_cov_idx + std::max(1, h->NE), d_rbase, h->lz.d_cov_rec, rcam, rcnt, S_, ld_,
                           h->lz.d_cov_pts);
       HIP_OK(hipStreamSynchronize(s));  // rbase's host copy goes out of scope
+      xr = CovRecs{true, d_rbase, rcnt, rcam, h->lz.d_cov_rec, S_, ld_};
     } else {
       // d_Y (the step's camera-major Y planes, unused on this route) takes the merged records
       launch_cov_points(s, v, NC > 0 && h->NE > 0, h->d_L, h->lz.d_Yrec, h->d_Y, h->lz.d_cov_idx,
                         h->lz.d_cov_idx + std::max(1, h->NE), h->d_S, h->lds, h->lz.d_cov_pts);
+      xr = CovRecs{NC > 0 && h->NE > 0, h->d_pt_ent_ptr, h->lz.d_cov_idx + std::max(1, h->NE), h->lz.d_cov_idx, h->d_Y,
+                   h->d_S, h->lds};
     }
   }
   HIP_OK(hipEventRecord(h->cov_ev[4], s));
+  CovxPlan xplan;
+  if (want_x) CHECK_RC(cov_blocks_run(h, *xb, nfi, xr, &xplan));
   double* d_ext21 = nullptr;
   if (want_c && (ext_cov || intr_cov || ext_full)) {
     if (ext_cov || intr_cov) {
@@ -827,6 +995,12 @@ static int covariance_impl(dab_handle* h, const dab_covariance_options* opt_in, 
   }
   HIP_OK(hipStreamSynchronize(s));
   // every array is written from here on, after the last check that can fail
+  if (want_x) {
+    float xms = 0.f;
+    HIP_OK(hipEventElapsedTime(&xms, h->cov_ev_x[0], h->cov_ev_x[1]));
+    if (xb->ms) *xb->ms = xms;
+    cov_blocks_write(*xb, xplan);
+  }
   if (point_cov) {
     const size_t npts = (size_t)h->prob.num_points;
     std::fill(point_cov, point_cov + 6 * npts, std::numeric_limits<double>::quiet_NaN());
@@ -853,5 +1027,15 @@ extern "C" int dab_covariance_intrinsics(dab_handle* h, const dab_covariance_opt
                                          dab_covariance_info* info, dab_covariance_intr_info* zinfo) {
   const int rc = covariance_impl(h, opt, point_cov, ext_cov, intr_cov, cam_full, info, zinfo, true);
   if (h) CHECK_RC(guard_fail(h, "dab_covariance_intrinsics"));
+  return rc;
+}
+extern "C" int dab_covariance_blocks(dab_handle* h, const dab_covariance_options* opt,
+                                     const dab_cov_blocks_request* req, double* pp_cov, double* pe_cov,
+                                     double* pz_cov, dab_covariance_info* info, dab_covariance_intr_info* zinfo,
+                                     double* blocks_ms) {
+  if (blocks_ms) *blocks_ms = 0.0;
+  const CovBlocks xb{req, pp_cov, pe_cov, pz_cov, blocks_ms};
+  const int rc = covariance_impl(h, opt, nullptr, nullptr, nullptr, nullptr, info, zinfo, true, &xb);
+  if (h) CHECK_RC(guard_fail(h, "dab_covariance_blocks"));
   return rc;
 }

@@ -306,6 +306,7 @@ struct Handle {
   std::vector<int> perm;            // sorted obs -> caller's obs index
   std::vector<int> pt_of;           // local point -> caller's point id
   std::vector<int> ext_col;         // ext -> free camera column
+  std::vector<uint8_t> ext_fixed;   // ext is constant (ext_const or freeze_camera): known exactly
   int nchunk = 0, nxchunk = 0, ncross = 0, nblk = 0, nslice = 0;
   int max_seg_chunks = 1, max_xseg_chunks = 1;  // largest chunk count of one camera / cross pair
   int NS = 0;  // observation slots (SELL-64, incl. padding)
@@ -458,6 +459,11 @@ struct Handle {
     double *d_covZz = nullptr, *d_cov_rec = nullptr;
     int* d_cov_ridx = nullptr;
     size_t covZz_cap = 0, cov_rec_cap = 0;
+    // dab_covariance_blocks: the translated pair lists [pp | pe | pz] and their blocks
+    // [pp 9 | pe 18 | pz 18 each], kept while they fit
+    int2* d_covx_pairs = nullptr;
+    double* d_covx_out = nullptr;
+    size_t covx_pairs_cap = 0, covx_out_cap = 0;
   } lz;
   double *d_points = nullptr, *d_points_c = nullptr, *d_ext = nullptr, *d_ext_c = nullptr;
   double *d_camtab = nullptr, *d_camtab_c = nullptr;
@@ -467,6 +473,7 @@ struct Handle {
   // events of the covariance's stage times, and around its border rows
   hipEvent_t cov_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   hipEvent_t cov_ev_z[2] = {nullptr, nullptr};
+  hipEvent_t cov_ev_x[2] = {nullptr, nullptr};  // around the cross-block kernels
   double* d_camred = nullptr;  // [Ucc NC*21 | gc NC*6 | Ux ncross*36] (all-reduced)
   double* d_partial = nullptr; // chunk partials (max of chunk counts * 36)
   double* d_xpartial = nullptr; // cross-block chunk partials
@@ -568,6 +575,8 @@ struct Handle {
     for (hipEvent_t e : cov_ev)
       if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : cov_ev_z)
+      if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : cov_ev_x)
       if (e) (void)hipEventDestroy(e);
     for (auto& e : bench_ev)
       for (hipEvent_t x : e) (void)hipEventDestroy(x);

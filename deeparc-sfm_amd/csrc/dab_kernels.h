@@ -586,6 +586,19 @@ void launch_cov_points_z(hipStream_t s, const DevView& v, bool with_cams, const 
 void launch_cov_unscale_z(hipStream_t s, int NC, int nfi, const double* scale_c, const double* sz, const int* act,
                           double* C, int ldc, double* blocks);
 
+// ---- cross blocks of the covariance (dab_covariance_blocks; dab_k_covx.hip) --------------------
+// The fold-back for a list of pairs over the record store of launch_cov_points(_z): rbase [NP]
+// (pt_ent_ptr without free intrinsics), rcnt [NP], rec [.][18], rcam; C the scaled (C') inverse
+// before the unscale. pairs[i].x < 0: skipped (the host answers). pc: pairs = (device point,
+// column block < NC + nfi), out [npairs][18] = -PU (sum Z_r^T C_c(r)c) diag(s), s = (sc, sz), +0 in
+// a column of scale 0. pp: pairs = (p <= p'), out [npairs][9] = PU_p (delta I + sum sum Z_r^T C
+// Z_r') PU_p'^T; with_recs = false: delta PU PU^T.
+void launch_covx_pc(hipStream_t s, int npairs, const int2* pairs, const int* rbase, const int* rcnt,
+                    const double* rec, const int* rcam, const double* PU, const double* C, int ldc, int NC,
+                    const double* sc, const double* sz, double* out);
+void launch_covx_pp(hipStream_t s, int npairs, const int2* pairs, bool with_recs, const int* rbase, const int* rcnt,
+                    const double* rec, const int* rcam, const double* PU, const double* C, int ldc, double* out);
+
 int grid_for(int n, int block, int cap);
 
 }  // namespace dab

@@ -158,9 +158,11 @@ static int setup_host(dab_handle* h, const dab_problem* p, PhaseTimer& phase) {
     eref.pop_back();
   }
   h->ext_col.assign(p->num_ext, -1);
+  h->ext_fixed.assign(p->num_ext, 0);
   h->NC = 0;
   for (int e = 0; e < p->num_ext; ++e) {
     const bool is_const = p->freeze_camera || (p->ext_const && p->ext_const[e]);
+    h->ext_fixed[e] = is_const;
     if (eref[e] != 0.0 && !is_const) h->ext_col[e] = h->NC++;
   }
   const int NP = h->NP, NC = h->NC;
@@ -769,9 +771,11 @@ static int setup_device(dab_handle* h, const dab_problem* p, PhaseTimer& phase) 
 
   // ---- free cameras (host: E is small) ----
   h->ext_col.assign(E, -1);
+  h->ext_fixed.assign(E, 0);
   h->NC = 0;
   for (int e = 0; e < E; ++e) {
     const bool is_const = p->freeze_camera || (p->ext_const && p->ext_const[e]);
+    h->ext_fixed[e] = is_const;
     if (eref[e] != 0 && !is_const) h->ext_col[e] = h->NC++;
   }
   const int NC = h->NC;

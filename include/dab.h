@@ -647,7 +647,8 @@ int dab_filter(dab_handle* h, double error_boundary, const double center[3], dou
  * sqrt(rho') exactly as dab_solve scales them. The covariance is Sigma = (J^T J)^-1, undamped
  * and without a sigma^2 factor: info->cost and the degrees of freedom (num_residuals -
  * num_parameters) let the caller multiply by 2 cost / dof. Returned are the diagonal blocks of
- * Sigma and, optionally, its whole camera part:
+ * Sigma and, optionally, its whole camera part (the blocks between two points, or between a point
+ * and an extrinsic or an intrinsic: dab_covariance_blocks):
  *   point_cov [num_points][6]   upper-packed 00 01 02 11 12 22, caller's point order; rows of
  *                               points referenced by no observation on this rank are NaN
  *   ext_cov   [num_free_ext][21] upper-packed 6x6 per free extrinsic, ascending extrinsic index
@@ -768,6 +769,59 @@ typedef struct dab_covariance_intr_info {
 int dab_covariance_intrinsics(dab_handle* h, const dab_covariance_options* opt /* NULL = defaults */,
                               double* point_cov, double* ext_cov, double* intr_cov, double* cam_full,
                               dab_covariance_info* info, dab_covariance_intr_info* zinfo);
+
+/* ---- cross blocks of the covariance ------------------------------------------------------------
+ * The blocks of Sigma that involve a point and something else, for a caller-given list of pairs:
+ * what ceres::Covariance answers for any two parameter blocks and the two calls above leave out
+ * (the pairs of two cameras are in ext_full / cam_full).
+ *   pp_cov [num_pp][9]   Sigma_ab, row-major 3x3, rows point a, columns point b
+ *   pe_cov [num_pe][18]  Sigma_pe, row-major 3x6, rows the point, columns w0 w1 w2 t0 t1 t2
+ *   pz_cov [num_pz][18]  Sigma_pz, row-major 3x6, rows the point, columns cx cy f0 f1 k0 k1
+ * Points are the caller's point ids, extrinsics and intrinsics the problem's indices (not the
+ * positions in ext_cov / intr_cov). Duplicates and (a, a) are allowed. The block (a, b) is bitwise
+ * the transpose of the block (b, a): both are one computation, and (a, a) is symmetric bitwise.
+ * (a, a) is point_cov's block within the accuracy of the route, not bitwise (the two sum in
+ * different orders).
+ *
+ * Which Sigma: one call serves both kinds of handle. With an empty free set it is dab_covariance's
+ * Sigma, with a non-empty one dab_covariance_intrinsics's, with their options, their rank test,
+ * info and zinfo, loss, priors, constant points, constant extrinsic scalars and freeze_camera: the
+ * call is theirs with the fold-back run for the pairs ("Covariance cross blocks").
+ *
+ * Known exactly, written as +0: a block with a constant point (dab_set_points_constant); a pe block
+ * of a constant extrinsic (ext_const, freeze_camera); the columns of constant extrinsic scalars
+ * (dab_set_ext_scalars_constant) and of inactive intrinsic slots; a pz block of an intrinsic that
+ * is not in the free set. No information, written as NaN (as point_cov's rows): a block with a
+ * point referenced by no observation on this rank, and a pe block of a non-constant extrinsic that
+ * nothing references. NaN goes before +0 where both apply.
+ *
+ * req NULL or all three counts 0: the size and rank query (info, zinfo). A list with count > 0 and
+ * a NULL index or output array, a negative count, or an index out of range: DAB_E_INVALID, nothing
+ * written, state unchanged. The other refusals are those of the two calls above (more than 16 free
+ * intrinsics, a non-empty free set without a free extrinsic: DAB_E_UNSUPPORTED). On
+ * DAB_COV_RANK_DEFICIENT no array is written. blocks_ms (nullable): the device time of the
+ * cross-block kernels (HIP events; 0 when none ran); info->points_ms is the point blocks' fold-back,
+ * which runs here too (it builds the records the pairs read).
+ *
+ * The pair lists are translated on the host and uploaded once per call; device scratch is lazy and
+ * freed by dab_set_problem and dab_destroy. Two calls in a row give bitwise equal arrays; a
+ * dab_solve after the call walks bitwise the trajectory it would have walked without it; the two
+ * calls above return bitwise what they return without it. Collective on a multi-rank handle: each
+ * rank asks about its own shard's points (a point of another rank is NaN), the camera side is
+ * identical on all ranks. */
+typedef struct dab_cov_blocks_request {
+  int32_t num_pp; const int32_t* pp;   /* [num_pp][2] caller's point ids (a, b)            */
+  int32_t num_pe; const int32_t* pe;   /* [num_pe][2] (caller's point id, extrinsic index) */
+  int32_t num_pz; const int32_t* pz;   /* [num_pz][2] (caller's point id, intrinsic index) */
+} dab_cov_blocks_request;
+
+int dab_covariance_blocks(dab_handle* h, const dab_covariance_options* opt /* NULL = defaults */,
+                          const dab_cov_blocks_request* req,
+                          double* pp_cov /* [num_pp][9]  row-major 3x3, rows a, cols b        */,
+                          double* pe_cov /* [num_pe][18] row-major 3x6, cols w0 w1 w2 t0 t1 t2 */,
+                          double* pz_cov /* [num_pz][18] row-major 3x6, cols cx cy f0 f1 k0 k1 */,
+                          dab_covariance_info* info, dab_covariance_intr_info* zinfo,
+                          double* blocks_ms /* nullable: device time of the new kernels */);
 
 /* Dense SPD solve A x = b on the handle's device with the library's blocked Cholesky (the
  * reduced-camera-system factorisation of DAB_LINEAR_SOLVER_EXPLICIT_SCHUR; Eigen LLT in
